@@ -23,6 +23,14 @@ reference publishes.
 Driver contract: ``python bench.py --gpus N --steps K --warmup W``; under
 torchrun each rank runs an independent shard (weak scaling) and rank 0
 reports the worst rank's p50.
+
+A plain run sets up the shard, warms up, times the K steps and prints the
+result line — nothing else.  ``--dump-outputs DIR`` additionally reads
+back, after the timed steps, the PRELOAD keys from the final primary and
+sync and saves them (plus the last step's lost-write count) as
+``DIR/<name>.npy``; the keys and values written are the same in every
+run, so two builds can be compared array for array.  ``--full`` is where
+any measurement beyond the headline figure belongs (none exists yet).
 """
 
 import argparse
@@ -43,6 +51,10 @@ from manatee_amd.tools.devcluster import DevCluster  # noqa: E402
 # reference's own test tier uses 2000 ms sessions
 # (/root/reference/test/zookeeperMgr.test.js:52-56); we use the same.
 SESSION_TIMEOUT_MS = 2000
+
+# writes acknowledged before the first kill of every run (keys
+# bench-0 .. bench-(PRELOAD-1)); --dump-outputs reads exactly these back
+PRELOAD = 50
 
 
 class Writer:
@@ -241,9 +253,41 @@ async def one_failover(cluster: DevCluster, writer: Writer) -> dict:
             "lost_acked_writes": v["lost"], "acked_checked": v["checked"]}
 
 
+async def read_back_preload(cluster: DevCluster) -> dict:
+    """What a caller is left with after the last timed step: the current
+    primary's (and sync's) values for the PRELOAD keys.  These keys are
+    acknowledged before the first kill in every run, so the arrays have
+    the same shape and — absent write loss — the same content from run
+    to run; a missing key reads back as NaN."""
+    s = await cluster.cluster_state()
+    out = {}
+    for role in ("primary", "sync"):
+        vals = []
+        if s.get(role):
+            cli = cluster.peer_by_id(s[role]["id"]).db_client()
+            try:
+                for i in range(PRELOAD):
+                    v = await cli.get("bench-%d" % i)
+                    vals.append(float("nan") if v is None else float(v))
+            finally:
+                await cli.close()
+        out["readback_%s" % role] = vals
+    return out
+
+
+def dump_outputs(dump_dir: str, arrays: dict) -> None:
+    """Write each array as ``<dump_dir>/<name>.npy`` (float64)."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, vals in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"),
+                np.asarray(vals, dtype=np.float64))
+
+
 async def run_rank(rank: int, steps: int, warmup: int, base_dir: str,
                    engine: str = "waldb",
-                   session_timeout_ms: int = SESSION_TIMEOUT_MS) -> dict:
+                   session_timeout_ms: int = SESSION_TIMEOUT_MS,
+                   want_outputs: bool = False) -> dict:
     cluster = DevCluster(os.path.join(base_dir, "rank%d" % rank),
                          n_peers=3, shard_name="%d.bench" % (rank + 1),
                          engine=engine,
@@ -271,7 +315,7 @@ async def run_rank(rank: int, steps: int, warmup: int, base_dir: str,
         writer = Writer(cluster)
         writer.start()
         # let some write load accumulate
-        while writer.seq < 50:
+        while writer.seq < PRELOAD:
             await asyncio.sleep(0.05)
 
         for i in range(warmup):
@@ -290,6 +334,11 @@ async def run_rank(rank: int, steps: int, warmup: int, base_dir: str,
                      r["acked_checked"]), file=sys.stderr)
         elapsed = time.monotonic() - t0
         await writer.stop()
+        outputs = None
+        if want_outputs:
+            outputs = await read_back_preload(cluster)
+            outputs["lost_acked_writes"] = \
+                [results[-1]["lost_acked_writes"]]
     finally:
         cluster.stop()
 
@@ -304,6 +353,7 @@ async def run_rank(rank: int, steps: int, warmup: int, base_dir: str,
         "checked": total_checked,
         "writes_acked": sum(r["acked_checked"] for r in results[-1:]),
         "elapsed_s": elapsed,
+        "outputs": outputs,
     }
 
 
@@ -322,7 +372,18 @@ def main() -> int:
                     help="ZK session timeout (failure-detection bound); "
                          "2000 matches the reference's test tier, 60000 "
                          "its production tier")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step "
+                         "left behind as DIR/<name>.npy (float64): the "
+                         "PRELOAD keys read back from the primary and the "
+                         "sync, and the last step's lost-write count")
+    ap.add_argument("--full", action="store_true",
+                    help="also run measurements beyond the headline "
+                         "figure (none at present: a plain run already "
+                         "does only setup, warmup and the timed steps)")
     ns = ap.parse_args()
+    if ns.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -331,10 +392,17 @@ def main() -> int:
     try:
         res = asyncio.run(run_rank(
             rank, ns.steps, ns.warmup, base_dir, engine=ns.engine,
-            session_timeout_ms=ns.session_timeout_ms))
+            session_timeout_ms=ns.session_timeout_ms,
+            want_outputs=ns.dump_outputs is not None))
     finally:
         if ns.workdir is None:   # keep logs when an explicit workdir is given
             shutil.rmtree(base_dir, ignore_errors=True)
+
+    if ns.dump_outputs is not None:
+        # one shard per rank: rank 0 owns the plain names
+        dump_outputs(ns.dump_outputs if rank == 0 else
+                     os.path.join(ns.dump_outputs, "rank%d" % rank),
+                     res.pop("outputs"))
 
     if world > 1:
         import torch.distributed as dist

@@ -6,7 +6,9 @@ MockState generator in /root/reference/test/tst.manateeAdm.js — same
 uuids, ips, replication rows and lag values), feeds them to OUR CLI via
 the MANATEE_ADM_TEST_STATE seam, formats the results in the reference's
 catest capture format, and diffs the whole thing byte-for-byte against
-/root/reference/test/tst.manateeAdm.js.out.
+the reference's expected output (its test/tst.manateeAdm.js.out), stored
+verbatim as the fixture ``tests/golden/ref_manatee_adm.out`` so the test
+needs nothing outside the repository.
 
 This is the strongest possible parity evidence for the committed
 `manatee-adm` surface (BASELINE.json: "manatee-adm output ...
@@ -20,10 +22,8 @@ import os
 import subprocess
 import sys
 
-import pytest
-
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_GOLDEN = "/root/reference/test/tst.manateeAdm.js.out"
+REF_GOLDEN = os.path.join(REPO, "tests", "golden", "ref_manatee_adm.out")
 
 # the reference's hardcoded peer uuids (test/tst.manateeAdm.js:180-191)
 UUIDS = [
@@ -240,9 +240,8 @@ def generate_output(tmp_path):
     return "".join(chunks)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_GOLDEN),
-                    reason="reference golden not available")
 def test_reference_golden_byte_identical(tmp_path):
+    assert os.path.exists(REF_GOLDEN), "committed fixture missing"
     got = generate_output(tmp_path)
     with open(REF_GOLDEN) as f:
         want = f.read()
