@@ -16,19 +16,22 @@ parsed as a libpq startup packet.
 
 from __future__ import annotations
 
+import argparse
 import asyncio
+import dataclasses
 import datetime
 import os
 import re
 import struct
 import sys
-import time
 from typing import Dict, List, Optional, Tuple
 
 from ...common import confparser
 from ...common import lsn as lsnmod
 from ...common.logging import Logger, level_from_verbosity
 from ...common.lsn import pg_strip_minor
+from ..waldb.core import (Settings, conf_value, init_data_dir as waldb_init,
+                          parse_knobs, run_server)
 from ..waldb.server import WaldbServer
 
 _I32 = struct.Struct(">i")
@@ -84,11 +87,11 @@ class PgSqlError(Exception):
 
 class MinipgServer(WaldbServer):
     PID_FILE = "postmaster.pid"
+    CONF_FILE = CONF_NAME
 
     def __init__(self, data_dir: str, log: Logger):
         super().__init__(data_dir, log)
         self.log = log.child(component="minipg")
-        self._trigger_file: Optional[str] = None
         try:
             with open(os.path.join(self.data_dir, "PG_VERSION")) as f:
                 self.pg_major = f.read().strip() or "12"
@@ -97,20 +100,10 @@ class MinipgServer(WaldbServer):
         self.lsn_word = "lsn" if float(self.pg_major) >= 10 else "location"
 
     # -------------------------------------------------- postgres conf model
-    def conf_path(self) -> str:
-        return os.path.join(self.data_dir, CONF_NAME)
-
-    def trigger_path(self) -> str:
-        if self._trigger_file:
-            return self._trigger_file
-        return os.path.join(os.path.dirname(self.data_dir), "promote")
-
-    def load_conf(self) -> None:
-        raw = confparser.read(self.conf_path())
-        s = self._strip
-        standby = False
-        conninfo_s = None
-        trigger = None
+    def read_settings(self, prev: Settings) -> Settings:
+        raw = confparser.read(os.path.join(self.data_dir, CONF_NAME))
+        s = conf_value
+        standby, conninfo_s, trigger = False, None, None
         rec_path = os.path.join(self.data_dir, RECOVERY_NAME)
         if os.path.exists(os.path.join(self.data_dir, SIGNAL_NAME)):
             # PG ≥12 style: standby.signal + settings in postgresql.conf
@@ -129,34 +122,22 @@ class MinipgServer(WaldbServer):
         listen = s(raw.get("listen_addresses", "127.0.0.1"))
         if listen in ("*", ""):
             listen = "0.0.0.0"
-        self.conf = {
-            "role": "standby" if standby else "primary",
-            "listen_ip": listen,
-            "port": s(raw.get("port", "5432")),
-            "name": ci.get("application_name", "standby"),
-        }
-        self.role = self.conf["role"]
-        self.read_only = s(raw.get("default_transaction_read_only",
-                                   "off")) == "on"
-        sync = s(raw.get("synchronous_standby_names", ""))
-        self.sync_standby = sync or None
-        self.upstream = None
+        upstream = None
         if standby and ci.get("host"):
-            self.upstream = "%s:%s" % (ci["host"], ci.get("port", "5432"))
-        self._trigger_file = trigger or None
-        try:
-            self.ckpt_wal_bytes = int(s(raw.get(
-                "checkpoint_wal_bytes", str(self.ckpt_wal_bytes))))
-            self.wal_keep_bytes = int(s(raw.get(
-                "wal_keep_bytes", str(self.wal_keep_bytes))))
-            self.wal.segment_bytes = int(s(raw.get(
-                "wal_segment_bytes", str(self.wal.segment_bytes))))
-            # PG expresses wal_sender_timeout in milliseconds
-            self.wal_sender_timeout_s = float(s(raw.get(
-                "wal_sender_timeout",
-                str(int(self.wal_sender_timeout_s * 1000))))) / 1000.0
-        except ValueError:
-            pass
+            upstream = "%s:%s" % (ci["host"], ci.get("port", "5432"))
+        # absent knobs keep their value; PG writes wal_sender_timeout in ms
+        return parse_knobs(raw, dataclasses.replace(
+            prev,
+            role="standby" if standby else "primary",
+            listen_ip=listen,
+            port=s(raw.get("port", "5432")),
+            name=ci.get("application_name", "standby"),
+            read_only=s(raw.get("default_transaction_read_only",
+                                "off")) == "on",
+            sync_standby=s(raw.get("synchronous_standby_names", "")) or None,
+            upstream=upstream,
+            trigger_path=trigger or os.path.join(
+                os.path.dirname(self.data_dir), "promote")), 0.001)
 
     # ------------------------------------------------- connection multiplex
     async def _handle_conn(self, reader: asyncio.StreamReader,
@@ -168,13 +149,7 @@ class MinipgServer(WaldbServer):
             return
         if first == b"{":
             # waldb JSON exchange (peer replication / internal probes)
-            try:
-                line = first + await reader.readline()
-            except (ConnectionError, asyncio.IncompleteReadError):
-                writer.close()
-                return
-            await self._serve_json(reader, writer, first_line=line)
-            return
+            return await self._serve_json(reader, writer, first)
         await self._serve_libpq(first, reader, writer)
 
     # ----------------------------------------------------- libpq v3 backend
@@ -201,6 +176,11 @@ class MinipgServer(WaldbServer):
 
     def _complete(self, tag: str) -> bytes:
         return self._msg(b"C", tag.encode() + b"\x00")
+
+    def _result(self, cols: List[str], rows: List[list]) -> List[bytes]:
+        """A whole SELECT answer: description, rows, completion tag."""
+        return ([self._row_desc(cols)] + [self._data_row(r) for r in rows]
+                + [self._complete("SELECT %d" % len(rows))])
 
     def _error(self, code: str, msg: str) -> bytes:
         fields = b"SERROR\x00" + b"C" + code.encode() + b"\x00" + \
@@ -332,7 +312,7 @@ class MinipgServer(WaldbServer):
         m = self._RE_DELETE.search(stmt)
         if m:
             k = sql_unquote(m.group(1))
-            if k not in self.kv:
+            if not self.get(k)[0]:
                 return [self._complete("DELETE 0")], None
             lsn = self._append_sql({"op": "del", "k": k}, "DELETE")
             return [self._complete("DELETE 1")], lsn
@@ -371,36 +351,30 @@ class MinipgServer(WaldbServer):
 
         if "current_time" in low and "from" not in low:
             now = datetime.datetime.now(datetime.timezone.utc)
-            return [self._row_desc(["current_time"]),
-                    self._data_row([now.strftime("%H:%M:%S.%f%z")]),
-                    self._complete("SELECT 1")]
+            return self._result(["current_time"],
+                                [[now.strftime("%H:%M:%S.%f%z")]])
 
         if "pg_is_in_recovery" in low:
-            return [self._row_desc(["r"]),
-                    self._data_row(["t" if self.role == "standby"
-                                    else "f"]),
-                    self._complete("SELECT 1")]
+            return self._result(
+                ["r"], [["t" if self.role == "standby" else "f"]])
 
         if "pg_current_wal_lsn" in low or "pg_current_xlog_location" in low:
             if self.role == "standby":
                 raise PgSqlError("55000", "recovery is in progress")
-            return [self._row_desc(["loc"]),
-                    self._data_row([lsnmod.format_lsn(self.wal.end)]),
-                    self._complete("SELECT 1")]
+            return self._result(["loc"],
+                                [[lsnmod.format_lsn(self.wal.end)]])
 
         if "pg_last_wal_replay_lsn" in low or \
                 "pg_last_xlog_replay_location" in low:
             val = (lsnmod.format_lsn(self.replay_lsn)
                    if self.role == "standby" else None)
-            return [self._row_desc(["loc"]), self._data_row([val]),
-                    self._complete("SELECT 1")]
+            return self._result(["loc"], [[val]])
 
         if "pg_last_xact_replay_timestamp" in low:
             val = ("%f" % self.last_replay_time
                    if (self.role == "standby" and self.last_replay_time)
                    else None)
-            return [self._row_desc(["t"]), self._data_row([val]),
-                    self._complete("SELECT 1")]
+            return self._result(["t"], [[val]])
 
         if "pg_stat_wal_receiver" in low:
             # the standby-side receiver status (real PG ≥9.6): one row
@@ -408,37 +382,25 @@ class MinipgServer(WaldbServer):
             # extension (real PG surfaces divergence only in its log);
             # the manager uses it to trigger the restore-on-divergence
             # path (ref standby-failure ⇒ restore :1339-1373).
-            cols = ["status", "conninfo"]
-            out = [self._row_desc(cols)]
+            rows = []
             if self.role == "standby":
                 status = {"streaming": "streaming",
                           "diverged": "diverged"}.get(
                               self.upstream_status, "stopped")
-                out.append(self._data_row(
-                    [status, "host=%s" % (self.upstream or "")]))
-                out.append(self._complete("SELECT 1"))
-            else:
-                out.append(self._complete("SELECT 0"))
-            return out
+                rows.append([status, "host=%s" % (self.upstream or "")])
+            return self._result(["status", "conninfo"], rows)
 
         if "pg_stat_replication" in low:
             return self._stat_replication()
 
         m = self._RE_SELECT_V.search(stmt)
         if m:
-            k = sql_unquote(m.group(1))
-            if k in self.kv:
-                return [self._row_desc(["v"]),
-                        self._data_row([str(self.kv[k])]),
-                        self._complete("SELECT 1")]
-            return [self._row_desc(["v"]), self._complete("SELECT 0")]
+            found, v = self.get(sql_unquote(m.group(1)))
+            return self._result(["v"], [[str(v)]] if found else [])
         m = self._RE_COUNT.search(stmt)
         if m:
-            prefix = sql_unquote(m.group(1) or "")
-            n = sum(1 for k in self.kv if k.startswith(prefix)) \
-                if prefix else len(self.kv)
-            return [self._row_desc(["count"]), self._data_row([str(n)]),
-                    self._complete("SELECT 1")]
+            n = self.count(sql_unquote(m.group(1) or ""))
+            return self._result(["count"], [[str(n)]])
         raise PgSqlError("42601", 'syntax error at or near "%s"'
                          % stmt.split()[0][:40])
 
@@ -447,26 +409,19 @@ class MinipgServer(WaldbServer):
         cols = ["pid", "application_name", "client_addr", "state",
                 "sent_" + w, "write_" + w, "flush_" + w, "replay_" + w,
                 "sync_state"]
-        out = [self._row_desc(cols)]
-        n = 0
-        for rep in self.replicas:
+        rows = []
+        for rep, row in self.replica_rows():
             addr = None
             try:
                 peer = rep.writer.get_extra_info("peername")
                 addr = peer[0] if peer else None
             except Exception:
                 pass
-            out.append(self._data_row([
-                str(os.getpid()), rep.name, addr, "streaming",
-                lsnmod.format_lsn(rep.sent_lsn),
-                lsnmod.format_lsn(rep.write_lsn),
-                lsnmod.format_lsn(rep.flush_lsn),
-                lsnmod.format_lsn(rep.replay_lsn),
-                "sync" if rep.name == self.sync_standby else "async",
-            ]))
-            n += 1
-        out.append(self._complete("SELECT %d" % n))
-        return out
+            rows.append([
+                str(os.getpid()), row["application_name"], addr,
+                row["state"], row["sent_lsn"], row["write_lsn"],
+                row["flush_lsn"], row["replay_lsn"], row["sync_state"]])
+        return self._result(cols, rows)
 
 
 # ---------------------------------------------------------------- binaries
@@ -474,16 +429,12 @@ class MinipgServer(WaldbServer):
 def init_data_dir(data_dir: str, version: str) -> None:
     """The initdb analogue: PG_VERSION (major), system identity,
     timeline 1 (ref _prepareDatabase lib/postgresMgr.js:1806-1987)."""
-    from ..waldb.server import init_data_dir as waldb_init
-    os.makedirs(data_dir, exist_ok=True)
     waldb_init(data_dir)
     with open(os.path.join(data_dir, "PG_VERSION"), "w") as f:
         f.write(pg_strip_minor(version) + "\n")
-    os.chmod(data_dir, 0o700)
 
 
 def initdb_main(version: str, argv=None) -> int:
-    import argparse
     ap = argparse.ArgumentParser(prog="initdb (minipg)")
     ap.add_argument("-D", "--pgdata", required=True)
     ap.add_argument("-E", "--encoding", default="UTF8")
@@ -499,8 +450,6 @@ def initdb_main(version: str, argv=None) -> int:
 
 
 def postgres_main(version: str, argv=None) -> int:
-    import argparse
-    import signal
     ap = argparse.ArgumentParser(prog="postgres (minipg)")
     ap.add_argument("-D", "--pgdata", required=True)
     ns, _ = ap.parse_known_args(argv)
@@ -508,26 +457,12 @@ def postgres_main(version: str, argv=None) -> int:
     log = Logger("minipg", level=level_from_verbosity(1),
                  path=os.path.join(os.path.dirname(data_dir),
                                    "minipg.log"))
-
-    async def run():
-        srv = MinipgServer(data_dir, log)
-        await srv.start()
-        stop = asyncio.Event()
-        loop = asyncio.get_running_loop()
-        # dirty-kill discipline: exit fast on any stop signal; the WAL
-        # is the only durability story (MANATEE-188)
-        for sig in (signal.SIGINT, signal.SIGTERM, signal.SIGQUIT):
-            loop.add_signal_handler(sig, stop.set)
-        await stop.wait()
-        return 0
-
-    return asyncio.run(run())
+    return run_server(MinipgServer(data_dir, log))
 
 
 def main(argv=None) -> int:
     """module entry: ``python -m manatee_amd.db.minipg -D dir
     [--init] [--pg-version 12.0]``."""
-    import argparse
     ap = argparse.ArgumentParser(prog="minipg")
     ap.add_argument("-D", "--pgdata", required=True)
     ap.add_argument("--init", action="store_true")
