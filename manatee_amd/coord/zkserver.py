@@ -15,6 +15,10 @@ A real ZooKeeper ensemble can be substituted 1:1 — the client side
 The store is in-memory with an optional append-only journal for restart
 durability (``journal_path``).  Coordination data is tiny (one state JSON +
 election nodes + history); the journal replays in milliseconds.
+
+This server is one process and therefore a single point of failure for
+failover.  ``zkquorum.py`` runs the same tree and front-end as a
+replicated three-member ensemble.
 """
 
 from __future__ import annotations
@@ -44,12 +48,13 @@ class _Node:
                  "mtime", "version", "cversion", "ephemeral_owner", "next_seq",
                  "pzxid")
 
-    def __init__(self, data: bytes, czxid: int, ephemeral_owner: int = 0):
+    def __init__(self, data: bytes, czxid: int, ephemeral_owner: int = 0,
+                 now_ms: Optional[int] = None):
         self.data = data
         self.children: Set[str] = set()
         self.stat_czxid = czxid
         self.stat_mzxid = czxid
-        self.ctime = _now_ms()
+        self.ctime = _now_ms() if now_ms is None else now_ms
         self.mtime = self.ctime
         self.version = 0
         self.cversion = 0
@@ -301,8 +306,12 @@ class ZkServer:
                     pass
 
     # ------------------------------------------------------------- core ops
+    # zxid / now_ms: the standalone server draws both locally (None).  The
+    # quorum server (zkquorum.py) passes the values its replicated txn
+    # carries, so every replica builds byte-identical Stats.
     def _do_create(self, path: str, data: bytes, flags: int, owner_sid: int,
-                   journal: bool = True) -> str:
+                   journal: bool = True, zxid: Optional[int] = None,
+                   now_ms: Optional[int] = None) -> str:
         _validate_path(path)
         parent_path = _parent(path)
         parent = self.nodes.get(parent_path)
@@ -315,10 +324,11 @@ class ZkServer:
             parent.next_seq += 1
         if path in self.nodes:
             raise ZkError(ZNODEEXISTS, path)
-        self.zxid += 1
+        self.zxid = self.zxid + 1 if zxid is None else zxid
         ephemeral = flags in (jute.EPHEMERAL, jute.EPHEMERAL_SEQUENTIAL)
         node = _Node(data, self.zxid,
-                     ephemeral_owner=owner_sid if ephemeral else 0)
+                     ephemeral_owner=owner_sid if ephemeral else 0,
+                     now_ms=now_ms)
         self.nodes[path] = node
         parent.children.add(path[len(parent_path):].lstrip("/"))
         parent.cversion += 1
@@ -333,7 +343,7 @@ class ZkServer:
         return path
 
     def _do_delete(self, path: str, version: int, force: bool = False,
-                   journal: bool = True) -> None:
+                   journal: bool = True, zxid: Optional[int] = None) -> None:
         node = self.nodes.get(path)
         if node is None:
             raise ZkError(ZNONODE, path)
@@ -341,7 +351,7 @@ class ZkServer:
             raise ZkError(ZNOTEMPTY, path)
         if version != -1 and version != node.version and not force:
             raise ZkError(ZBADVERSION, path)
-        self.zxid += 1
+        self.zxid = self.zxid + 1 if zxid is None else zxid
         del self.nodes[path]
         parent_path = _parent(path)
         parent = self.nodes.get(parent_path)
@@ -358,16 +368,17 @@ class ZkServer:
         self._fire_child_watch(parent_path)
 
     def _do_set_data(self, path: str, data: bytes, version: int,
-                     journal: bool = True) -> Stat:
+                     journal: bool = True, zxid: Optional[int] = None,
+                     now_ms: Optional[int] = None) -> Stat:
         node = self.nodes.get(path)
         if node is None:
             raise ZkError(ZNONODE, path)
         if version != -1 and version != node.version:
             raise ZkError(ZBADVERSION, path)
-        self.zxid += 1
+        self.zxid = self.zxid + 1 if zxid is None else zxid
         node.data = data
         node.version += 1
-        node.mtime = _now_ms()
+        node.mtime = _now_ms() if now_ms is None else now_ms
         node.stat_mzxid = self.zxid
         if journal and not node.ephemeral_owner:
             self._journal_write({"op": "setData", "path": path,

@@ -5,7 +5,8 @@ per-peer directories and configs (ports stepped +10 per peer like the
 reference, ref docs/working-on-manatee.md:179-197), spawns the embedded ZK
 server, and one sitter + backupserver (+ optional snapshotter) pair per
 peer as real subprocesses.  Used by the integration tests, ``bench.py``
-and ``tools/mkdevsitters``.
+and ``tools/mkdevsitters``.  ``zk_ensemble=3`` replaces the single
+coordination server with three ``coord/zkquorum`` member processes.
 """
 
 from __future__ import annotations
@@ -349,7 +350,9 @@ class DevCluster:
                  snapshot_number: int = 5,
                  proxied: bool = False,
                  storage_provider: str = "dir",
-                 pg_version: str = "12"):
+                 pg_version: str = "12",
+                 zk_ensemble: int = 1,
+                 zk_election_timeout_ms: tuple = (500, 1000)):
         self.base_dir = os.path.abspath(base_dir)
         self.ip = ip
         self.engine = engine
@@ -390,6 +393,26 @@ class DevCluster:
         self.peers.clear()
         self.zk_port = zk_peer.pg_port
         self.zk_conn_str = "%s:%d" % (ip, self.zk_port)
+        # zk_ensemble > 1: that many coordination members (coord/zkquorum),
+        # each with its own port block (client port, quorum port) and data
+        # directory; the connection string lists every client address
+        if zk_ensemble < 1 or (zk_ensemble > 1 and zk_ensemble % 2 == 0):
+            raise ValueError("zk_ensemble must be 1 or an odd number")
+        self.zk_ensemble = zk_ensemble
+        self.zk_election_timeout_ms = tuple(zk_election_timeout_ms)
+        self.zk_members: List[dict] = []
+        if zk_ensemble > 1:
+            blocks = [zk_peer]
+            for _ in range(zk_ensemble - 1):
+                blocks.append(self.add_peer_config())
+                self.peers.clear()
+            for i, blk in enumerate(blocks):
+                self.zk_members.append({
+                    "id": i + 1, "client_port": blk.pg_port,
+                    "quorum_port": blk.status_port, "proc": None,
+                    "dir": os.path.join(self.base_dir, "zk%d" % (i + 1))})
+            self.zk_conn_str = ",".join(
+                "%s:%d" % (ip, m["client_port"]) for m in self.zk_members)
         for _ in range(n_peers):
             self.add_peer_config()
 
@@ -439,6 +462,10 @@ class DevCluster:
 
     # -------------------------------------------------------------- control
     def start_zk(self) -> None:
+        if self.zk_ensemble > 1:
+            for i in range(self.zk_ensemble):
+                self.start_zk_member(i)
+            return
         env = dict(os.environ)
         env["PYTHONPATH"] = REPO_ROOT + os.pathsep + \
             env.get("PYTHONPATH", "")
@@ -452,7 +479,10 @@ class DevCluster:
 
     def kill_zk(self) -> None:
         """SIGKILL the coordination server (full-ZK outage tier of the
-        reference's chaos plan, docs/test-plan.md)."""
+        reference's chaos plan, docs/test-plan.md).  In ensemble mode:
+        every member."""
+        for i in range(len(self.zk_members)):
+            self.kill_zk_member(i)
         if self.zk_proc is not None and self.zk_proc.poll() is None:
             try:
                 os.killpg(self.zk_proc.pid, signal.SIGKILL)
@@ -462,6 +492,10 @@ class DevCluster:
         self.zk_proc = None
 
     async def wait_zk(self, timeout_s: float = 15.0) -> None:
+        if self.zk_ensemble > 1:
+            # an ensemble is "up" when a leader is serving clients
+            await self.wait_zk_leader(timeout_s)
+            return
         deadline = time.monotonic() + timeout_s
         while True:
             try:
@@ -472,6 +506,89 @@ class DevCluster:
                 if time.monotonic() > deadline:
                     raise RuntimeError("zk server did not start")
                 await asyncio.sleep(0.05)
+
+    # ------------------------------------------- coordination ensemble
+    def start_zk_member(self, i: int) -> None:
+        m = self.zk_members[i]
+        if m["proc"] is not None and m["proc"].poll() is None:
+            return
+        env = dict(os.environ)
+        env["PYTHONPATH"] = REPO_ROOT + os.pathsep + \
+            env.get("PYTHONPATH", "")
+        os.makedirs(self.base_dir, exist_ok=True)
+        logf = open(os.path.join(self.base_dir, "zk%d.log" % m["id"]), "a")
+        peers = ",".join("%d=%s:%d" % (o["id"], self.ip, o["quorum_port"])
+                         for o in self.zk_members)
+        m["proc"] = subprocess.Popen(
+            [sys.executable, "-m", "manatee_amd.coord.zkquorum",
+             "--id", str(m["id"]),
+             "--client", "%s:%d" % (self.ip, m["client_port"]),
+             "--peers", peers, "--data-dir", m["dir"],
+             "--election-timeout-ms",
+             "%d,%d" % self.zk_election_timeout_ms, "-v"],
+            env=env, stdout=logf, stderr=logf, start_new_session=True)
+
+    def kill_zk_member(self, i: int) -> None:
+        """SIGKILL one coordination member."""
+        m = self.zk_members[i]
+        proc = m["proc"]
+        if proc is not None and proc.poll() is None:
+            try:
+                os.killpg(proc.pid, signal.SIGKILL)
+            except ProcessLookupError:
+                pass
+            proc.wait()
+        m["proc"] = None
+
+    async def _zk_srvr(self, i: int) -> Optional[dict]:
+        """One member's answer to the ``srvr`` four-letter word, as a
+        dict of its ``Key: value`` lines; None when it does not answer."""
+        m = self.zk_members[i]
+        writer = None
+        try:
+            reader, writer = await asyncio.wait_for(
+                asyncio.open_connection(self.ip, m["client_port"]), 2.0)
+            writer.write(b"srvr")
+            await writer.drain()
+            text = (await asyncio.wait_for(reader.read(), 2.0)).decode()
+        except (OSError, asyncio.TimeoutError):
+            return None
+        finally:
+            if writer is not None:
+                writer.close()
+        return dict(line.split(": ", 1) for line in text.splitlines()
+                    if ": " in line)
+
+    async def zk_roles(self) -> List[Optional[str]]:
+        """``leader`` / ``follower`` / ``candidate`` per member, None
+        for one that is down."""
+        out = []
+        for i in range(len(self.zk_members)):
+            info = await self._zk_srvr(i)
+            out.append(info.get("Mode") if info else None)
+        return out
+
+    async def zk_leader_index(self) -> Optional[int]:
+        """Index of the member that is leader AND serving clients."""
+        best = None
+        for i in range(len(self.zk_members)):
+            info = await self._zk_srvr(i)
+            if info and info.get("Mode") == "leader" and \
+                    info.get("Serving") == "yes":
+                if best is None or int(info["Epoch"]) > best[0]:
+                    best = (int(info["Epoch"]), i)
+        return best[1] if best else None
+
+    async def wait_zk_leader(self, timeout_s: float = 15.0) -> int:
+        deadline = time.monotonic() + timeout_s
+        while True:
+            i = await self.zk_leader_index()
+            if i is not None:
+                return i
+            if time.monotonic() > deadline:
+                raise RuntimeError("no coordination leader; roles=%r"
+                                   % (await self.zk_roles(),))
+            await asyncio.sleep(0.05)
 
     async def start(self, peers: Optional[List[int]] = None) -> None:
         if self.proxied:
@@ -492,10 +609,22 @@ class DevCluster:
         (ref docs/test-plan.md:24-113)."""
         from .netproxy import LinkProxy
         for src in self.peers:
-            pz = LinkProxy(self.ip, self.zk_port,
-                           name="peer%d->zk" % src.index)
-            await pz.start()
-            self.proxies[(src.index, "zk")] = pz
+            dmap = {}
+            if self.zk_ensemble > 1:
+                # one proxy per (peer, coordination member)
+                for m in self.zk_members:
+                    pz = LinkProxy(self.ip, m["client_port"],
+                                   name="peer%d->zk%d" % (src.index,
+                                                          m["id"]))
+                    await pz.start()
+                    self.proxies[(src.index, "zk", m["id"])] = pz
+                    dmap["%s:%d" % (self.ip, m["client_port"])] = pz.addr
+            else:
+                pz = LinkProxy(self.ip, self.zk_port,
+                               name="peer%d->zk" % src.index)
+                await pz.start()
+                self.proxies[(src.index, "zk")] = pz
+                dmap["%s:%d" % (self.ip, self.zk_port)] = pz.addr
             for dst in self.peers:
                 if dst.index == src.index:
                     continue
@@ -508,7 +637,6 @@ class DevCluster:
                     self.proxies[(src.index, dst.index, kind)] = p
             # the dial map must exist before the peer spawns
             os.makedirs(src.dir, exist_ok=True)
-            dmap = {"%s:%d" % (self.ip, self.zk_port): pz.addr}
             for dst in self.peers:
                 if dst.index == src.index:
                     continue
@@ -547,14 +675,18 @@ class DevCluster:
     def partition_zk(self, a: DevPeer) -> None:
         """Cut peer a off from the coordination server (its session
         expires) while leaving every peer↔peer link intact."""
-        p = self.proxies.get((a.index, "zk"))
-        if p is not None:
+        for p in self._zk_proxies(a):
             p.set_drops(to_server=True, to_client=True)
 
     def heal_zk(self, a: DevPeer) -> None:
-        p = self.proxies.get((a.index, "zk"))
-        if p is not None:
+        for p in self._zk_proxies(a):
             p.heal()
+
+    def _zk_proxies(self, a: DevPeer) -> list:
+        """Peer a's link(s) to the coordination plane: one in standalone
+        mode, one per member in ensemble mode."""
+        return [p for key, p in self.proxies.items()
+                if key[0] == a.index and key[1] == "zk"]
 
     def isolate(self, a: DevPeer) -> None:
         """Full network isolation of one peer (ZK + every peer link);
@@ -576,6 +708,8 @@ class DevCluster:
                 p._server.close()
             p.kill_connections()
         self.proxies.clear()
+        for i in range(len(self.zk_members)):
+            self.kill_zk_member(i)
         if self.zk_proc is not None and self.zk_proc.poll() is None:
             try:
                 os.killpg(self.zk_proc.pid, signal.SIGKILL)
@@ -688,12 +822,16 @@ def main(argv=None) -> int:
     ap.add_argument("--singleton", action="store_true",
                     help="one peer in one-node-write mode")
     ap.add_argument("--session-timeout-ms", type=int, default=10000)
+    ap.add_argument("--zk-ensemble", type=int, default=1,
+                    help="coordination members (1 = standalone server, "
+                         "3 = replicated ensemble)")
     ns = ap.parse_args(argv)
 
     async def run():
         c = DevCluster(ns.dir, n_peers=ns.peers, shard_name=ns.shard,
                        singleton=ns.singleton or ns.peers == 1,
-                       session_timeout_ms=ns.session_timeout_ms)
+                       session_timeout_ms=ns.session_timeout_ms,
+                       zk_ensemble=ns.zk_ensemble)
         await c.start()
         print("zk:     %s" % c.zk_conn_str)
         print("shard:  %s" % c.shard_path)

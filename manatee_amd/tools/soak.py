@@ -3,7 +3,7 @@ synchronous write load with randomized faults, verifying zero
 acknowledged-write loss after every cycle.
 
     python -m manatee_amd.tools.soak --minutes 10 [--cycles 50]
-        [--seed 7] [-d DIR]
+        [--seed 7] [-d DIR] [--zk-ensemble 3]
 
 Faults drawn each cycle: SIGKILL primary / sync / async, SIGKILL just
 the database child (sitter must restart it), SIGSTOP+SIGCONT the
@@ -13,6 +13,11 @@ asymmetric ack loss; tools/netproxy).  After every fault the shard must
 converge back to writable with every previously-acknowledged write
 present (writer frozen, exact server-side count + recent-window
 readback), then the shard is healed to full primary/sync/async shape.
+With ``--zk-ensemble N`` (N > 1) coordination is a replicated ensemble
+(coord/zkquorum) and two more faults join the draw: SIGKILL of the
+coordination leader and of a coordination follower; ``max_zk_failover_s``
+then records the longest time from killing the leader until another
+member serves.
 One JSON summary line on stdout at the end; exit 1 on any lost write
 or convergence failure.
 """
@@ -190,16 +195,23 @@ async def dump_stall(cluster: DevCluster, action: str) -> None:
 ACTIONS = ["kill_primary", "kill_sync", "kill_async",
            "kill_db_only", "pause_primary", "zk_outage",
            "partition_zk_primary", "partition_repl", "partition_asym"]
+# joined to the draw only when coordination is an ensemble, so that the
+# seeded sequence of a default run never changes
+ZK_ENSEMBLE_ACTIONS = ["kill_zk_leader", "kill_zk_follower"]
 
 
 async def soak(minutes: float, seed: int, workdir: str,
                cycles: Optional[int] = None,
-               engine: str = "waldb") -> dict:
+               engine: str = "waldb", zk_ensemble: int = 1) -> dict:
     rng = random.Random(seed)
     c = DevCluster(workdir, n_peers=3, shard_name="1.soak", proxied=True,
-                   engine=engine)
+                   engine=engine, zk_ensemble=zk_ensemble)
     stats = {"cycles": 0, "kills": {}, "lost": 0, "acked": 0,
              "max_failover_s": 0.0, "failures": []}
+    actions = list(ACTIONS)
+    if zk_ensemble > 1:
+        actions += ZK_ENSEMBLE_ACTIONS
+        stats["max_zk_failover_s"] = 0.0
     writer = SoakWriter(c)
     # SIGTERM (timeout-bounded runs) must unwind through the finally so
     # the cluster is torn down, not orphaned
@@ -225,7 +237,7 @@ async def soak(minutes: float, seed: int, workdir: str,
         while time.monotonic() < deadline and \
                 (cycles is None or stats["cycles"] < cycles):
             s = await c.cluster_state()
-            action = rng.choice(ACTIONS)
+            action = rng.choice(actions)
             stats["kills"][action] = stats["kills"].get(action, 0) + 1
             prim = c.peer_by_id(s["primary"]["id"])
             sync = c.peer_by_id(s["sync"]["id"])
@@ -249,6 +261,22 @@ async def soak(minutes: float, seed: int, workdir: str,
                 await asyncio.sleep(rng.uniform(1.0, 4.0))
                 c.start_zk()
                 await c.wait_zk()
+            elif action in ("kill_zk_leader", "kill_zk_follower"):
+                lead = await c.wait_zk_leader()
+                if action == "kill_zk_leader":
+                    member = lead
+                else:
+                    member = rng.choice([i for i in range(zk_ensemble)
+                                         if i != lead])
+                tz = time.monotonic()
+                c.kill_zk_member(member)
+                if action == "kill_zk_leader":
+                    await c.wait_zk_leader(timeout_s=60)
+                    stats["max_zk_failover_s"] = max(
+                        stats["max_zk_failover_s"],
+                        time.monotonic() - tz)
+                await asyncio.sleep(rng.uniform(1.0, 4.0))
+                c.start_zk_member(member)
             elif action == "partition_zk_primary":
                 # primary cut from ZK only: session expiry → sync
                 # takeover; the old primary is deposed on heal.  A
@@ -351,18 +379,24 @@ def main(argv=None) -> int:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--engine", choices=("waldb", "postgres"),
                     default="waldb")
+    ap.add_argument("--zk-ensemble", type=int, default=1,
+                    help="coordination members; above 1 adds the "
+                         "kill_zk_leader / kill_zk_follower faults")
     ap.add_argument("-d", "--dir", default=None)
     ns = ap.parse_args(argv)
     workdir = ns.dir or tempfile.mkdtemp(prefix="manatee-soak-")
     try:
         stats = asyncio.run(soak(ns.minutes, ns.seed, workdir,
-                                 cycles=ns.cycles, engine=ns.engine))
+                                 cycles=ns.cycles, engine=ns.engine,
+                                 zk_ensemble=ns.zk_ensemble))
     finally:
         if ns.dir is None:
             shutil.rmtree(workdir, ignore_errors=True)
     ok = not stats["lost"] and not stats["failures"]
     stats["ok"] = ok
     stats["engine"] = ns.engine
+    if ns.zk_ensemble > 1:
+        stats["zk_ensemble"] = ns.zk_ensemble
     print(json.dumps(stats))
     return 0 if ok else 1
 
