@@ -33,6 +33,7 @@ from ...common.lsn import pg_strip_minor
 from ..waldb.core import (Settings, conf_value, init_data_dir as waldb_init,
                           parse_knobs, run_server)
 from ..waldb.server import WaldbServer
+from ..waldb.wal import encode_op
 
 _I32 = struct.Struct(">i")
 _I16 = struct.Struct(">h")
@@ -41,6 +42,10 @@ SSL_REQUEST = 80877103
 CANCEL_REQUEST = 80877102
 GSSENC_REQUEST = 80877104
 PROTOCOL_V3 = 196608
+
+# largest libpq message accepted; also the cap on one transaction
+# block's buffered (encoded) writes
+MAX_MSG = 16 * 1024 * 1024
 
 CONF_NAME = "postgresql.conf"
 RECOVERY_NAME = "recovery.conf"
@@ -78,11 +83,95 @@ def split_statements(sql: str) -> List[str]:
     return [s.strip() for s in out if s.strip()]
 
 
+# a whole single-quoted literal ('' is an escaped quote)
+_RE_LITERAL = re.compile(r"'(?:[^']|'')*'")
+# a literal (an unterminated one runs to the end) or a $n placeholder
+_RE_PARAM = re.compile(r"'(?:[^']|'')*(?:'|$)|\$(\d+)")
+
+
+def count_params(sql: str) -> int:
+    """The highest ``$n`` outside single-quoted literals."""
+    top = 0
+    for m in _RE_PARAM.finditer(sql):
+        if m.group(1) is not None:
+            n = int(m.group(1))
+            if n < 1:
+                raise PgSqlError("42P02", "there is no parameter $0")
+            top = max(top, n)
+    return top
+
+
+def bind_params(sql: str, params: List[Optional[str]]) -> str:
+    """Lexical parameter substitution: every ``$n`` outside a literal
+    becomes a quoted literal with ``'`` doubled (``NULL`` for None).  One
+    pass, so a ``$1`` inside a substituted VALUE is never looked at
+    again, and a value cannot close its own literal."""
+    def rep(m):
+        if m.group(1) is None:
+            return m.group(0)
+        v = params[int(m.group(1)) - 1]
+        return "NULL" if v is None else "'" + v.replace("'", "''") + "'"
+    return _RE_PARAM.sub(rep, sql)
+
+
+def _cstr(buf: bytes, pos: int) -> Tuple[str, int]:
+    end = buf.index(b"\x00", pos)
+    return buf[pos:end].decode("utf-8"), end + 1
+
+
 class PgSqlError(Exception):
     def __init__(self, code: str, msg: str):
         self.code = code
         self.msg = msg
         super().__init__(msg)
+
+
+_TOMBSTONE = object()       # a key deleted inside the open block
+
+
+class _Portal:
+    __slots__ = ("stmt", "kind", "cols", "arg", "rows", "pos")
+
+    def __init__(self, stmt: str, kind: str, cols, arg):
+        self.stmt = stmt            # name of the statement it was bound to
+        self.kind = kind
+        self.cols = cols
+        self.arg = arg
+        self.rows: Optional[List[list]] = None      # None until executed
+        self.pos = 0
+
+
+class _Session:
+    """Per-connection state: the transaction block with its buffered
+    writes, and the extended-query protocol's statements, portals and
+    staged output.  It dies with the connection, so a client that drops
+    mid-block leaves no trace."""
+
+    __slots__ = ("txn", "ops", "ops_bytes", "pending", "stmts", "portals",
+                 "staged", "max_lsn", "skip")
+
+    def __init__(self):
+        self.txn = "I"              # ReadyForQuery status: I, T or E
+        self.ops: List[dict] = []
+        self.ops_bytes = 0
+        self.pending: Dict[str, object] = {}
+        self.stmts: Dict[str, Tuple[str, int, Optional[List[str]]]] = {}
+        self.portals: Dict[str, _Portal] = {}
+        self.staged: List[bytes] = []
+        self.max_lsn: Optional[int] = None
+        self.skip = False           # discarding until the next Sync
+
+    def end_txn(self) -> None:
+        self.txn = "I"
+        self.ops = []
+        self.ops_bytes = 0
+        self.pending = {}
+        self.portals.clear()
+
+    def fail(self) -> None:
+        """An error inside a block fails the block."""
+        if self.txn == "T":
+            self.txn = "E"
 
 
 class MinipgServer(WaldbServer):
@@ -174,8 +263,16 @@ class MinipgServer(WaldbServer):
                 body.append(_I32.pack(len(b)) + b)
         return self._msg(b"D", b"".join(body))
 
+    # the CommandComplete frames of the fixed tags, built once
+    _COMPLETE = {
+        tag: b"C" + _I32.pack(len(tag) + 5) + tag.encode() + b"\x00"
+        for tag in ("INSERT 0 1", "DELETE 1", "DELETE 0", "UPDATE 1",
+                    "UPDATE 0", "SELECT 1", "SELECT 0", "BEGIN", "COMMIT",
+                    "ROLLBACK", "CREATE TABLE")}
+
     def _complete(self, tag: str) -> bytes:
-        return self._msg(b"C", tag.encode() + b"\x00")
+        return self._COMPLETE.get(tag) or \
+            self._msg(b"C", tag.encode() + b"\x00")
 
     def _result(self, cols: List[str], rows: List[list]) -> List[bytes]:
         """A whole SELECT answer: description, rows, completion tag."""
@@ -187,13 +284,12 @@ class MinipgServer(WaldbServer):
             b"M" + msg.encode() + b"\x00" + b"\x00"
         return self._msg(b"E", fields)
 
-    def _ready(self) -> bytes:
-        return self._msg(b"Z", b"I")
+    def _ready(self, status: str = "I") -> bytes:
+        return self._msg(b"Z", status.encode())
 
     async def _serve_libpq(self, first: bytes,
                            reader: asyncio.StreamReader,
                            writer: asyncio.StreamWriter) -> None:
-        MAX_MSG = 16 * 1024 * 1024
         try:
             while True:     # startup negotiation (SSL probe then startup)
                 rest = await reader.readexactly(3)
@@ -231,6 +327,7 @@ class MinipgServer(WaldbServer):
             writer.write(b"".join(out))
             await writer.drain()
 
+            sess = _Session()
             while True:
                 hdr = await reader.readexactly(5)
                 t = hdr[:1]
@@ -243,15 +340,21 @@ class MinipgServer(WaldbServer):
                 payload = await reader.readexactly(ln - 4)
                 if t == b"X":
                     return
-                if t != b"Q":
+                if t == b"Q":
+                    if sess.staged or sess.skip:
+                        # a simple query ends an unsynced extended sequence
+                        await self._flush_staged(sess, writer, sync=False)
+                        sess.skip = False
+                    sql = payload.rstrip(b"\x00").decode("utf-8")
+                    await self._run_query_cycle(sql, writer, sess)
+                elif t in self._EXTENDED:
+                    await self._extended(t, payload, sess, writer)
+                else:
                     writer.write(self._error(
-                        "0A000", "only the simple query protocol is "
-                        "supported"))
-                    writer.write(self._ready())
+                        "0A000", "unsupported frontend message %r"
+                        % t.decode("latin-1")))
+                    writer.write(self._ready(sess.txn))
                     await writer.drain()
-                    continue
-                sql = payload.rstrip(b"\x00").decode("utf-8")
-                await self._run_query_cycle(sql, writer)
         except (asyncio.IncompleteReadError, ConnectionError,
                 asyncio.CancelledError):
             pass
@@ -264,7 +367,8 @@ class MinipgServer(WaldbServer):
                 pass
 
     async def _run_query_cycle(self, sql: str,
-                               writer: asyncio.StreamWriter) -> None:
+                               writer: asyncio.StreamWriter,
+                               sess: _Session) -> None:
         """One simple-Query cycle: possibly multiple statements, one
         ReadyForQuery at the end; an error aborts the rest (as the real
         backend does).  GROUP COMMIT: every write in the statement list
@@ -276,7 +380,7 @@ class MinipgServer(WaldbServer):
         err: Optional[PgSqlError] = None
         for stmt in split_statements(sql) or [""]:
             try:
-                chunks, lsn = await self._execute_staged(stmt)
+                chunks, lsn = self._execute_staged(stmt, sess)
             except PgSqlError as exc:
                 err = exc
                 break
@@ -294,29 +398,24 @@ class MinipgServer(WaldbServer):
         for chunk in staged:
             writer.write(chunk)
         if err is not None:
+            sess.fail()
             writer.write(self._error(err.code, err.msg))
-        writer.write(self._ready())
+        writer.write(self._ready(sess.txn))
         await writer.drain()
 
-    async def _execute_staged(self, stmt: str
-                              ) -> Tuple[List[bytes], Optional[int]]:
-        """Writes append-without-waiting (their acks are withheld until
-        the cycle's single commit gate); everything else executes
+    def _execute_staged(self, stmt: str, sess: _Session
+                        ) -> Tuple[List[bytes], Optional[int]]:
+        """One statement of a simple-Query cycle as wire chunks.  Writes
+        append-without-waiting (their acks are withheld until the
+        cycle's single commit gate); everything else executes
         directly."""
-        m = self._RE_INSERT.search(stmt)
-        if m:
-            lsn = self._append_sql(
-                {"op": "put", "k": sql_unquote(m.group(1)),
-                 "v": sql_unquote(m.group(2))}, "INSERT")
-            return [self._complete("INSERT 0 1")], lsn
-        m = self._RE_DELETE.search(stmt)
-        if m:
-            k = sql_unquote(m.group(1))
-            if not self.get(k)[0]:
-                return [self._complete("DELETE 0")], None
-            lsn = self._append_sql({"op": "del", "k": k}, "DELETE")
-            return [self._complete("DELETE 1")], lsn
-        return await self._execute(stmt), None
+        kind, cols, arg = self._plan(stmt)
+        rows, tag, lsn = self._run(kind, arg, sess)
+        if cols is not None:
+            return self._result(cols, rows), lsn
+        if tag is None:
+            return [self._msg(b"I")], lsn       # EmptyQueryResponse
+        return [self._complete(tag)], lsn
 
     def _append_sql(self, op: dict, verb: str) -> int:
         lsn, err = self._append_write(op)
@@ -329,6 +428,205 @@ class MinipgServer(WaldbServer):
             raise PgSqlError("XX000", msg or "write failed")
         return lsn
 
+    # --------------------------------------------- extended-query protocol
+    _EXTENDED = frozenset((b"P", b"B", b"D", b"E", b"C", b"S", b"H"))
+
+    async def _extended(self, t: bytes, payload: bytes, sess: _Session,
+                        writer: asyncio.StreamWriter) -> None:
+        """One extended-protocol message.  All output is STAGED in the
+        session and reaches the socket only at Sync or Flush, behind one
+        commit gate for the highest LSN appended so far — the simple
+        path's durability rule: no CommandComplete for a write is sent
+        before its WAL record passed ``_await_commit``.  After an error
+        every message up to the next Sync is discarded."""
+        if t == b"S":
+            return await self._flush_staged(sess, writer, sync=True)
+        if t == b"H":
+            return await self._flush_staged(sess, writer, sync=False)
+        if sess.skip:
+            return
+        try:
+            try:
+                if t == b"P":
+                    self._on_parse(payload, sess)
+                elif t == b"B":
+                    self._on_bind(payload, sess)
+                elif t == b"D":
+                    self._on_describe(payload, sess)
+                elif t == b"E":
+                    self._on_execute(payload, sess)
+                else:
+                    self._on_close(payload, sess)
+            except (struct.error, ValueError, IndexError) as exc:
+                raise PgSqlError("08P01", "malformed %s message: %s"
+                                 % (t.decode(), exc))
+        except PgSqlError as exc:
+            sess.fail()
+            sess.staged.append(self._error(exc.code, exc.msg))
+            sess.skip = True
+
+    async def _flush_staged(self, sess: _Session,
+                            writer: asyncio.StreamWriter,
+                            sync: bool) -> None:
+        if sess.max_lsn is not None:
+            lsn, sess.max_lsn = sess.max_lsn, None
+            res = await self._await_commit(lsn)
+            if not res.get("ok"):
+                # as in _run_query_cycle: nothing staged may be
+                # acknowledged once the gate broke
+                sess.fail()
+                sess.staged = [self._error(
+                    "25006", res.get("error", "commit failed"))]
+                sess.skip = True
+        if sess.staged:
+            writer.write(b"".join(sess.staged))
+            sess.staged = []
+        if sync:
+            sess.skip = False
+            if sess.txn == "I":
+                sess.portals.clear()    # portals end with the transaction
+            writer.write(self._ready(sess.txn))
+        await writer.drain()
+
+    def _check_failed(self, sess: _Session, kind: str) -> None:
+        if sess.txn == "E" and kind not in ("commit", "rollback"):
+            raise PgSqlError(
+                "25P02", "current transaction is aborted, commands "
+                "ignored until end of transaction block")
+
+    def _on_parse(self, p: bytes, sess: _Session) -> None:
+        name, pos = _cstr(p, 0)
+        sql, pos = _cstr(p, pos)
+        # declared parameter type oids are ignored: everything is text
+        (ntypes,) = _I16.unpack_from(p, pos)
+        if ntypes < 0 or pos + 2 + 4 * ntypes > len(p):
+            raise ValueError("parameter type list runs past the message")
+        if name and name in sess.stmts:
+            raise PgSqlError("42P05", 'prepared statement "%s" already '
+                             'exists' % name)
+        parts = split_statements(sql)
+        if len(parts) > 1:
+            raise PgSqlError("42601", "cannot insert multiple commands "
+                             "into a prepared statement")
+        text = parts[0] if parts else ""
+        nparams = count_params(text)
+        # plan with empty literals in the parameters' places: what kind
+        # of statement this is never depends on a literal's content
+        kind, cols, _ = self._plan(bind_params(text, [""] * nparams))
+        self._check_failed(sess, kind)
+        sess.stmts[name] = (text, nparams, cols)
+        sess.staged.append(self._msg(b"1"))
+
+    def _on_bind(self, p: bytes, sess: _Session) -> None:
+        portal, pos = _cstr(p, 0)
+        stmt, pos = _cstr(p, pos)
+        (nfmt,) = _I16.unpack_from(p, pos)
+        fmts = struct.unpack_from(">%dh" % nfmt, p, pos + 2)
+        pos += 2 + 2 * nfmt
+        (nparams,) = _I16.unpack_from(p, pos)
+        pos += 2
+        raw: List[Optional[bytes]] = []
+        for _ in range(nparams):
+            (ln,) = _I32.unpack_from(p, pos)
+            pos += 4
+            if ln < 0:
+                raw.append(None)
+            else:
+                if pos + ln > len(p):
+                    raise ValueError("parameter runs past the message")
+                raw.append(p[pos:pos + ln])
+                pos += ln
+        (nres,) = _I16.unpack_from(p, pos)
+        fmts += struct.unpack_from(">%dh" % nres, p, pos + 2)
+        if stmt not in sess.stmts:
+            raise PgSqlError("26000", 'prepared statement "%s" does not '
+                             'exist' % stmt)
+        text, want, _cols = sess.stmts[stmt]
+        if nparams != want:
+            raise PgSqlError(
+                "08P01", 'bind message supplies %d parameters, but prepared '
+                'statement "%s" requires %d' % (nparams, stmt, want))
+        if any(fmts):
+            raise PgSqlError("0A000", "binary parameter and result "
+                             "formats are not supported")
+        if portal and portal in sess.portals:
+            raise PgSqlError("42P03", 'cursor "%s" already exists' % portal)
+        try:
+            params = [None if b is None else b.decode("utf-8") for b in raw]
+        except UnicodeDecodeError:
+            raise PgSqlError("22021", "invalid byte sequence for encoding "
+                             '"UTF8"')
+        kind, cols, arg = self._plan(bind_params(text, params))
+        self._check_failed(sess, kind)
+        sess.portals[portal] = _Portal(stmt, kind, cols, arg)
+        sess.staged.append(self._msg(b"2"))
+
+    def _on_describe(self, p: bytes, sess: _Session) -> None:
+        """Answered from the plan alone: nothing executes."""
+        what = p[:1]
+        name, _ = _cstr(p, 1)
+        if what == b"S":
+            if name not in sess.stmts:
+                raise PgSqlError("26000", 'prepared statement "%s" does '
+                                 'not exist' % name)
+            _text, nparams, cols = sess.stmts[name]
+            sess.staged.append(self._msg(
+                b"t", _I16.pack(nparams) + _I32.pack(25) * nparams))
+        elif what == b"P":
+            if name not in sess.portals:
+                raise PgSqlError("34000", 'portal "%s" does not exist'
+                                 % name)
+            cols = sess.portals[name].cols
+        else:
+            raise ValueError("describe target %r" % what)
+        sess.staged.append(self._row_desc(cols) if cols is not None
+                           else self._msg(b"n"))
+
+    def _on_execute(self, p: bytes, sess: _Session) -> None:
+        name, pos = _cstr(p, 0)
+        (max_rows,) = _I32.unpack_from(p, pos)
+        portal = sess.portals.get(name)
+        if portal is None:
+            raise PgSqlError("34000", 'portal "%s" does not exist' % name)
+        if portal.cols is None:
+            if portal.rows is not None:
+                raise PgSqlError("55000", 'portal "%s" cannot be run'
+                                 % name)
+            portal.rows = []
+            _rows, tag, lsn = self._run(portal.kind, portal.arg, sess)
+            if lsn is not None:
+                sess.max_lsn = lsn
+            sess.staged.append(self._complete(tag) if tag is not None
+                               else self._msg(b"I"))
+            return
+        if portal.rows is None:
+            portal.rows, _tag, _lsn = self._run(portal.kind, portal.arg,
+                                                sess)
+        left = len(portal.rows) - portal.pos
+        n = min(left, max_rows) if max_rows > 0 else left
+        for row in portal.rows[portal.pos:portal.pos + n]:
+            sess.staged.append(self._data_row(row))
+        portal.pos += n
+        if n < left:
+            sess.staged.append(self._msg(b"s"))     # PortalSuspended
+        else:
+            # the tag counts the rows of THIS Execute, as PostgreSQL's
+            sess.staged.append(self._complete("SELECT %d" % n))
+
+    def _on_close(self, p: bytes, sess: _Session) -> None:
+        what = p[:1]
+        name, _ = _cstr(p, 1)
+        if what == b"S":
+            if sess.stmts.pop(name, None) is not None:
+                for pname in [n for n, po in sess.portals.items()
+                              if po.stmt == name]:
+                    del sess.portals[pname]
+        elif what == b"P":
+            sess.portals.pop(name, None)
+        else:
+            raise ValueError("close target %r" % what)
+        sess.staged.append(self._msg(b"3"))
+
     # ------------------------------------------------------------ SQL layer
     _RE_INSERT = re.compile(
         r"insert\s+into\s+kv\s*\(\s*k\s*,\s*v\s*\)\s*values\s*\(\s*"
@@ -340,43 +638,193 @@ class MinipgServer(WaldbServer):
         r"(?:\s+where\s+k\s+like\s+'((?:[^']|'')*)%')?", re.I)
     _RE_DELETE = re.compile(
         r"delete\s+from\s+kv\s+where\s+k\s*=\s*'((?:[^']|'')*)'", re.I)
+    _RE_UPDATE = re.compile(
+        r"update\s+kv\s+set\s+v\s*=\s*'((?:[^']|'')*)'\s*"
+        r"where\s+k\s*=\s*'((?:[^']|'')*)'", re.I)
 
-    async def _execute(self, stmt: str) -> List[bytes]:
-        low = " ".join(stmt.lower().split())
+    _TXN_WORDS = {"begin": "begin", "commit": "commit", "end": "commit",
+                  "rollback": "rollback", "abort": "rollback"}
+
+    @staticmethod
+    def _verb(rx, stmt: str):
+        """``rx`` found in ``stmt`` as the statement itself.  A match
+        with a quote before it lies inside or behind a literal — the
+        TEXT of a key or value, never the command."""
+        m = rx.search(stmt)
+        if m is not None and m.start() and "'" in stmt[:m.start()]:
+            return None
+        return m
+
+    def _plan(self, stmt: str):
+        """What a statement is, without running it:
+        ``(kind, columns, arg)``.  ``columns`` is None for a statement
+        that returns no rows, otherwise exactly the column names
+        ``_run``'s rows come with — Describe answers from here."""
+        if stmt[:1] in "sS":
+            # the read hot path: a statement that BEGINS as a key lookup
+            # is one, without a look at the other patterns
+            m = self._RE_SELECT_V.match(stmt)
+            if m:
+                return "select_v", ["v"], sql_unquote(m.group(1))
+        m = self._RE_INSERT.search(stmt)        # _verb, inlined: hot
+        if m and not (m.start() and "'" in stmt[:m.start()]):
+            return "insert", None, (sql_unquote(m.group(1)),
+                                    sql_unquote(m.group(2)))
+        m = self._verb(self._RE_DELETE, stmt)
+        if m:
+            return "delete", None, sql_unquote(m.group(1))
+        m = self._verb(self._RE_UPDATE, stmt)
+        if m:
+            return "update", None, (sql_unquote(m.group(2)),
+                                    sql_unquote(m.group(1)))
+
+        # keywords are looked for outside literals only
+        low = stmt.lower()
+        if "'" in low:
+            low = _RE_LITERAL.sub("''", low)
+        low = " ".join(low.split())
         if not low:
-            return [self._msg(b"I")]        # EmptyQueryResponse
+            return "empty", None, None
+
+        word = low.split(" ", 1)[0]
+        if word in self._TXN_WORDS or low.startswith("start transaction"):
+            if "savepoint" in low or low.startswith("rollback to"):
+                raise PgSqlError("0A000", "savepoints are not supported")
+            return self._TXN_WORDS.get(word, "begin"), None, None
 
         if low.startswith("create table"):
-            return [self._complete("CREATE TABLE")]
+            return "create", None, None
 
         if "current_time" in low and "from" not in low:
-            now = datetime.datetime.now(datetime.timezone.utc)
-            return self._result(["current_time"],
-                                [[now.strftime("%H:%M:%S.%f%z")]])
+            return "current_time", ["current_time"], None
 
         if "pg_is_in_recovery" in low:
-            return self._result(
-                ["r"], [["t" if self.role == "standby" else "f"]])
+            return "in_recovery", ["r"], None
 
         if "pg_current_wal_lsn" in low or "pg_current_xlog_location" in low:
-            if self.role == "standby":
-                raise PgSqlError("55000", "recovery is in progress")
-            return self._result(["loc"],
-                                [[lsnmod.format_lsn(self.wal.end)]])
+            return "current_lsn", ["loc"], None
 
         if "pg_last_wal_replay_lsn" in low or \
                 "pg_last_xlog_replay_location" in low:
-            val = (lsnmod.format_lsn(self.replay_lsn)
-                   if self.role == "standby" else None)
-            return self._result(["loc"], [[val]])
+            return "replay_lsn", ["loc"], None
 
         if "pg_last_xact_replay_timestamp" in low:
+            return "replay_ts", ["t"], None
+
+        if "pg_stat_wal_receiver" in low:
+            return "wal_receiver", ["status", "conninfo"], None
+
+        if "pg_stat_replication" in low:
+            w = self.lsn_word
+            return "stat_replication", [
+                "pid", "application_name", "client_addr", "state",
+                "sent_" + w, "write_" + w, "flush_" + w, "replay_" + w,
+                "sync_state"], None
+
+        m = self._verb(self._RE_SELECT_V, stmt)
+        if m:
+            return "select_v", ["v"], sql_unquote(m.group(1))
+        m = self._verb(self._RE_COUNT, stmt)
+        if m:
+            return "count", ["count"], sql_unquote(m.group(1) or "")
+        raise PgSqlError("42601", 'syntax error at or near "%s"'
+                         % stmt.split()[0][:40])
+
+    def _run(self, kind: str, arg, sess: _Session
+             ) -> Tuple[Optional[List[list]], Optional[str], Optional[int]]:
+        """Execute a planned statement: ``(rows, tag, lsn)``.  ``rows``
+        is None unless the plan has columns; ``tag`` is None for the
+        empty query and for row-returning statements (their tag is the
+        row count); ``lsn`` is the WAL position a write still has to
+        pass the commit gate for."""
+        if kind == "insert":
+            op = {"op": "put", "k": arg[0], "v": arg[1]}
+            if sess.txn == "I":
+                return None, "INSERT 0 1", self._append_sql(op, "INSERT")
+            self._buffer(sess, op, "INSERT")
+            return None, "INSERT 0 1", None
+
+        if kind == "select_v":
+            if sess.txn != "I":
+                self._check_failed(sess, kind)
+            found, v = self._txn_get(sess, arg)
+            return ([[str(v)]] if found else []), None, None
+
+        if sess.txn == "E":
+            self._check_failed(sess, kind)
+
+        if kind == "delete":
+            if not self._txn_get(sess, arg)[0]:
+                return None, "DELETE 0", None
+            op = {"op": "del", "k": arg}
+            if sess.txn == "I":
+                return None, "DELETE 1", self._append_sql(op, "DELETE")
+            self._buffer(sess, op, "DELETE")
+            return None, "DELETE 1", None
+
+        if kind == "update":
+            if not self._txn_get(sess, arg[0])[0]:
+                return None, "UPDATE 0", None
+            op = {"op": "put", "k": arg[0], "v": arg[1]}
+            if sess.txn == "I":
+                return None, "UPDATE 1", self._append_sql(op, "UPDATE")
+            self._buffer(sess, op, "UPDATE")
+            return None, "UPDATE 1", None
+
+        if kind == "count":
+            return [[str(self._txn_count(sess, arg))]], None, None
+
+        if kind == "begin":
+            if sess.txn == "I":
+                sess.txn = "T"
+            return None, "BEGIN", None
+
+        if kind == "commit":
+            was, ops = sess.txn, sess.ops
+            sess.end_txn()
+            if was == "E":
+                return None, "ROLLBACK", None
+            if not ops:
+                return None, "COMMIT", None
+            # the whole block is ONE WAL record: all-or-nothing across
+            # a crash and across replication
+            return None, "COMMIT", self._append_sql(
+                {"op": "batch", "ops": ops}, "COMMIT")
+
+        if kind == "rollback":
+            sess.end_txn()
+            return None, "ROLLBACK", None
+
+        if kind == "empty":
+            return None, None, None
+
+        if kind == "create":
+            return None, "CREATE TABLE", None
+
+        if kind == "current_time":
+            now = datetime.datetime.now(datetime.timezone.utc)
+            return [[now.strftime("%H:%M:%S.%f%z")]], None, None
+
+        if kind == "in_recovery":
+            return [["t" if self.role == "standby" else "f"]], None, None
+
+        if kind == "current_lsn":
+            if self.role == "standby":
+                raise PgSqlError("55000", "recovery is in progress")
+            return [[lsnmod.format_lsn(self.wal.end)]], None, None
+
+        if kind == "replay_lsn":
+            val = (lsnmod.format_lsn(self.replay_lsn)
+                   if self.role == "standby" else None)
+            return [[val]], None, None
+
+        if kind == "replay_ts":
             val = ("%f" % self.last_replay_time
                    if (self.role == "standby" and self.last_replay_time)
                    else None)
-            return self._result(["t"], [[val]])
+            return [[val]], None, None
 
-        if "pg_stat_wal_receiver" in low:
+        if kind == "wal_receiver":
             # the standby-side receiver status (real PG ≥9.6): one row
             # while this server is a standby.  'diverged' is a minipg
             # extension (real PG surfaces divergence only in its log);
@@ -388,27 +836,52 @@ class MinipgServer(WaldbServer):
                           "diverged": "diverged"}.get(
                               self.upstream_status, "stopped")
                 rows.append([status, "host=%s" % (self.upstream or "")])
-            return self._result(["status", "conninfo"], rows)
+            return rows, None, None
 
-        if "pg_stat_replication" in low:
-            return self._stat_replication()
+        if kind == "stat_replication":
+            return self._stat_replication(), None, None
 
-        m = self._RE_SELECT_V.search(stmt)
-        if m:
-            found, v = self.get(sql_unquote(m.group(1)))
-            return self._result(["v"], [[str(v)]] if found else [])
-        m = self._RE_COUNT.search(stmt)
-        if m:
-            n = self.count(sql_unquote(m.group(1) or ""))
-            return self._result(["count"], [[str(n)]])
-        raise PgSqlError("42601", 'syntax error at or near "%s"'
-                         % stmt.split()[0][:40])
+        raise PgSqlError("XX000", "unplanned statement kind %r" % kind)
 
-    def _stat_replication(self) -> List[bytes]:
-        w = self.lsn_word
-        cols = ["pid", "application_name", "client_addr", "state",
-                "sent_" + w, "write_" + w, "flush_" + w, "replay_" + w,
-                "sync_state"]
+    # ---------------------------------------------------- transaction block
+    def _buffer(self, sess: _Session, op: dict, verb: str) -> None:
+        """A write inside a block: nothing reaches the WAL before
+        COMMIT.  The read-only check is made here too, so the statement
+        fails where PostgreSQL's would, not only at COMMIT."""
+        if sess.txn == "E":
+            self._check_failed(sess, "write")
+        settings = self.settings
+        if settings.role != "primary" or settings.read_only:
+            raise PgSqlError(
+                "25006",
+                "cannot execute %s in a read-only transaction" % verb)
+        sess.ops_bytes += len(encode_op(op))
+        if sess.ops_bytes > MAX_MSG:
+            raise PgSqlError(
+                "54000", "transaction exceeds %d bytes of buffered writes"
+                % MAX_MSG)
+        sess.ops.append(op)
+        sess.pending[op["k"]] = op["v"] if op["op"] == "put" else _TOMBSTONE
+
+    def _txn_get(self, sess: _Session, k: str) -> Tuple[bool, object]:
+        """Committed state overlaid with the block's own writes."""
+        if sess.pending and k in sess.pending:
+            v = sess.pending[k]
+            return (False, None) if v is _TOMBSTONE else (True, v)
+        return self.get(k)
+
+    def _txn_count(self, sess: _Session, prefix: str) -> int:
+        n = self.count(prefix)
+        for k, v in sess.pending.items():
+            if prefix and not k.startswith(prefix):
+                continue
+            if v is _TOMBSTONE:
+                n -= k in self.kv
+            else:
+                n += k not in self.kv
+        return n
+
+    def _stat_replication(self) -> List[list]:
         rows = []
         for rep, row in self.replica_rows():
             addr = None
@@ -421,7 +894,7 @@ class MinipgServer(WaldbServer):
                 str(os.getpid()), row["application_name"], addr,
                 row["state"], row["sent_lsn"], row["write_lsn"],
                 row["flush_lsn"], row["replay_lsn"], row["sync_state"]])
-        return self._result(cols, rows)
+        return rows
 
 
 # ---------------------------------------------------------------- binaries
