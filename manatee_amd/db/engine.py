@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import os
 import sys
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 from ..common import confparser
 from ..common.logging import Logger, null_logger
@@ -96,7 +96,17 @@ class WaldbEngine(Engine):
     name = "waldb"
 
     def __init__(self, data_dir: str, ip: str, port: int, peer_name: str,
-                 log: Optional[Logger] = None):
+                 log: Optional[Logger] = None,
+                 tunables: Optional[Dict[str, object]] = None):
+        """``tunables``: waldb tuning knobs (``core.KNOB_NAMES``) written
+        into every regenerated conf — ``postgresMgrCfg.waldbTunables``,
+        the analogue of the postgres engine's pg_overrides."""
+        unknown = sorted(set(tunables or {}) - set(waldb_server.KNOB_NAMES))
+        if unknown:
+            raise ValueError("unknown waldb tunable(s) %s; known: %s"
+                             % (", ".join(unknown),
+                                ", ".join(waldb_server.KNOB_NAMES)))
+        self.tunables = {k: str(v) for k, v in (tunables or {}).items()}
         self.data_dir = data_dir
         self.ip = ip
         self.port = port
@@ -140,6 +150,7 @@ class WaldbEngine(Engine):
             conf["primary_conninfo"] = "'%s:%d'" % (host, port)
         if sync_name:
             conf["synchronous_standby_names"] = "'%s'" % sync_name
+        conf.update(self.tunables)
         confparser.write(self._conf_path(), conf)
 
     def write_promote_trigger(self) -> None:
@@ -186,6 +197,9 @@ class WaldbEngine(Engine):
 
     async def status(self) -> dict:
         return await self._cli().status()
+
+    async def checkpoint_info(self) -> dict:
+        return await self._cli().checkpoint_info()
 
     async def check_repl(self, standby_name: str) -> dict:
         st = await self.status()

@@ -198,6 +198,14 @@ class WaldbClient:
             raise WaldbError(resp.get("error", "status failed"))
         return resp
 
+    async def checkpoint_info(self) -> dict:
+        """Checkpoint mode, manifest LSN, layer files, dirty-key count
+        and the checkpoint/compaction counters."""
+        resp = await self.query({"q": "ckpt"})
+        if not resp.get("ok"):
+            raise WaldbError(resp.get("error", "ckpt failed"))
+        return resp
+
     async def xlog(self) -> str:
         resp = await self.query({"q": "xlog"})
         if not resp.get("ok"):

@@ -30,6 +30,8 @@ from typing import Dict, Iterator, List, Optional, Tuple
 from ...common import dial
 from ...common import lsn as lsnmod
 from ...common.logging import Logger
+from . import ckpt as ckptmod
+from .ckpt import CheckpointCorrupt, CheckpointFormatError  # noqa: F401
 from .wal import (DEFAULT_SEGMENT_BYTES, Wal, WalGone, _codec, encode_op,
                   decode_op, parse_frames)
 
@@ -47,6 +49,7 @@ DEFAULT_WAL_KEEP_BYTES = 32 * 1024 * 1024
 # PostgreSQL wal_sender_timeout defense: a SIGSTOPped/partitioned
 # standby must not pin WAL retention and a replica slot forever)
 DEFAULT_WAL_SENDER_TIMEOUT_S = 60.0
+CKPT_MODES = ("full", "incremental")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -65,6 +68,7 @@ class Settings:
     wal_keep_bytes: int = DEFAULT_WAL_KEEP_BYTES
     wal_segment_bytes: int = DEFAULT_SEGMENT_BYTES
     wal_sender_timeout_s: float = DEFAULT_WAL_SENDER_TIMEOUT_S
+    ckpt_mode: str = "full"                 # "full" | "incremental"
 
 
 def conf_value(v: str) -> str:
@@ -72,11 +76,19 @@ def conf_value(v: str) -> str:
     return v.strip().strip("'").strip('"')
 
 
+def _ckpt_mode(v: str) -> str:
+    if v not in CKPT_MODES:
+        raise ValueError("checkpoint_mode %r" % (v,))
+    return v
+
+
 # conf key, Settings field, parser — applied in this order
 _KNOBS = (("checkpoint_wal_bytes", "ckpt_wal_bytes", int),
           ("wal_keep_bytes", "wal_keep_bytes", int),
           ("wal_segment_bytes", "wal_segment_bytes", int),
-          ("wal_sender_timeout", "wal_sender_timeout_s", float))
+          ("wal_sender_timeout", "wal_sender_timeout_s", float),
+          ("checkpoint_mode", "ckpt_mode", _ckpt_mode))
+KNOB_NAMES = tuple(key for key, _field, _parse in _KNOBS)
 
 
 def parse_knobs(raw: Dict[str, str], fallback: Settings,
@@ -165,6 +177,18 @@ class ReplCore:
         self.ckpt_lsn = 0
         self._last_ckpt_bytes = 0
         self._ckpt_running = False
+        # keys touched since the last checkpoint (what an incremental
+        # checkpoint writes), the layers the manifest on disk names, and
+        # layer files a compaction superseded: those are unlinked one
+        # generation late, see _retire_layers
+        self._dirty: set = set()
+        self._layers: List[dict] = []
+        self._ckpt_garbage: List[str] = []
+        self._ckpt_count = 0
+        # of the last checkpoint: dirty keys it captured, records it wrote
+        self._last_ckpt_dirty = 0
+        self._last_ckpt_records = 0
+        self._compact_count = 0
         self.ident: dict = {}
         self.replay_lsn = 0
         self.last_replay_time: Optional[float] = None
@@ -395,13 +419,7 @@ class ReplCore:
                 if m != conf_mtime:
                     conf_mtime = m
                     self._on_sighup()
-            # adaptive spacing: a checkpoint serializes the WHOLE kv, so
-            # requiring at least half the last image's size in new WAL
-            # keeps checkpoint I/O amortized O(1) per WAL byte — a big
-            # database no longer re-dumps hundreds of MB every 8 MB of
-            # appends (recovery stays bounded by ~2x the image size)
-            ckpt_due = max(self.ckpt_wal_bytes, self._last_ckpt_bytes // 2)
-            if self.replay_lsn - self.ckpt_lsn >= ckpt_due \
+            if self.replay_lsn - self.ckpt_lsn >= self._ckpt_due_bytes() \
                     and not self._ckpt_running:
                 asyncio.get_running_loop().create_task(self._checkpoint())
 
@@ -411,9 +429,33 @@ class ReplCore:
         try:
             with open(path) as f:
                 ckpt = json.load(f)
+        except FileNotFoundError:
+            ckptmod.remove_unreferenced(self.data_dir, ())
+            return
         except (OSError, ValueError):
             return
-        self.kv = ckpt.get("kv", {})
+        # what is on disk decides, never the configured mode
+        if "kv" not in ckpt and "format" in ckpt:
+            if ckpt["format"] != ckptmod.MANIFEST_FORMAT:
+                self.log.error("checkpoint.json has an unknown format; "
+                               "REFUSING to start", format=ckpt["format"])
+                raise CheckpointFormatError(
+                    "checkpoint format %r" % (ckpt["format"],))
+            try:
+                self.kv, self._layers = ckptmod.load_layers(self.data_dir,
+                                                            ckpt)
+            except CheckpointCorrupt as exc:
+                # never serve the kv without a layer the manifest names
+                self.log.error("checkpoint layer corrupt; REFUSING to "
+                               "start (rebuild this peer)", err=exc)
+                raise
+        else:
+            self.kv = ckpt.get("kv", {})
+        removed = ckptmod.remove_unreferenced(
+            self.data_dir, [layer["name"] for layer in self._layers])
+        if removed:
+            self.log.info("removed unreferenced checkpoint files",
+                          files=sorted(removed))
         self.ckpt_lsn = int(ckpt.get("lsn", 0))
         self.replay_lsn = self.ckpt_lsn
         try:
@@ -422,7 +464,20 @@ class ReplCore:
             pass
         self.log.info("checkpoint loaded",
                       lsn=lsnmod.format_lsn(self.ckpt_lsn),
-                      keys=len(self.kv))
+                      keys=len(self.kv), layers=len(self._layers))
+
+    def _ckpt_due_bytes(self) -> int:
+        """New WAL after which the next checkpoint is due.
+
+        Full mode, adaptive spacing: a checkpoint serializes the WHOLE
+        kv, so requiring at least half the last image's size in new WAL
+        keeps checkpoint I/O amortized O(1) per WAL byte — a big database
+        no longer re-dumps hundreds of MB every 8 MB of appends (recovery
+        stays bounded by ~2x the image size).  An incremental checkpoint
+        costs O(dirty keys), so the configured spacing holds."""
+        if self.settings.ckpt_mode == "incremental":
+            return self.ckpt_wal_bytes
+        return max(self.ckpt_wal_bytes, self._last_ckpt_bytes // 2)
 
     async def _checkpoint(self) -> None:
         """Write an atomic point-in-time image of the kv state at the
@@ -438,14 +493,12 @@ class ReplCore:
             # positions on the same timeline.
             self.wal.fsync()
             at = self.replay_lsn
-            snap = dict(self.kv)   # single-threaded: consistent at `at`
-            path = os.path.join(self.data_dir, CKPT_NAME)
-            self._last_ckpt_bytes = \
-                await asyncio.get_running_loop().run_in_executor(
-                    None, lambda: _write_json_atomic(
-                        path, {"lsn": at, "kv": snap},
-                        separators=(",", ":")))
+            if self.settings.ckpt_mode == "incremental":
+                await self._checkpoint_incremental(at)
+            else:
+                await self._checkpoint_full(at)
             self.ckpt_lsn = at
+            self._ckpt_count += 1
             # retention floor: the checkpoint, minus the keep window,
             # and never past what a connected replica still needs
             keep = self.settings.wal_keep_bytes
@@ -467,16 +520,158 @@ class ReplCore:
                            wal_start=lsnmod.format_lsn(self.wal.start))
         except Exception as exc:
             self.log.error("checkpoint failed", err=exc)
+        else:
+            if self._compaction_due():
+                try:
+                    await self._compact()
+                except Exception as exc:
+                    # the layers and the manifest are as they were
+                    self.log.error("checkpoint compaction failed", err=exc)
         finally:
             self._ckpt_running = False
+
+    async def _checkpoint_full(self, at: int) -> None:
+        """The classic image: the whole kv in ``checkpoint.json``."""
+        captured, self._dirty = self._dirty, set()
+        snap = dict(self.kv)   # single-threaded: consistent at `at`
+        path = os.path.join(self.data_dir, CKPT_NAME)
+        try:
+            self._last_ckpt_bytes = \
+                await asyncio.get_running_loop().run_in_executor(
+                    None, lambda: _write_json_atomic(
+                        path, {"lsn": at, "kv": snap},
+                        separators=(",", ":")))
+        except BaseException:
+            self._dirty |= captured
+            raise
+        self._last_ckpt_dirty = len(captured)
+        self._last_ckpt_records = len(snap)
+        if self._layers or self._ckpt_garbage:
+            # switched back from incremental: the image supersedes the
+            # layers like a compaction does
+            names = [layer["name"] for layer in self._layers]
+            self._layers = []
+            await asyncio.get_running_loop().run_in_executor(
+                None, self._retire_layers, names)
+
+    async def _checkpoint_incremental(self, at: int) -> None:
+        """Write the keys touched since the last checkpoint as a delta
+        layer and publish a manifest that names it.  The event loop does
+        O(dirty keys) work; encoding and I/O happen in the executor.
+
+        The exception is the first checkpoint after the mode is turned
+        on (or after a classic image was loaded): there is no base yet,
+        so one is written from the live kv — once, O(dataset)."""
+        loop = asyncio.get_running_loop()
+        ckpt_dir = os.path.join(self.data_dir, ckptmod.CKPT_DIR)
+        captured, self._dirty = self._dirty, set()
+        try:
+            layers = list(self._layers)
+            written = 0
+            if not layers:
+                items = list(self.kv.items())
+                kind, parent = "base", 0
+            else:
+                kv, tomb = self.kv, ckptmod.TOMBSTONE
+                items = [(k, kv.get(k, tomb)) for k in captured]
+                kind, parent = "delta", layers[-1]["lsn"]
+            if kind == "base" or items:
+                if at <= parent and kind == "delta":
+                    raise RuntimeError("delta at %d not above layer at %d"
+                                       % (at, parent))
+                layer = await loop.run_in_executor(
+                    None, lambda: ckptmod.write_layer(
+                        ckpt_dir, kind, at, parent, items, len(items)))
+                layers.append(layer)
+                written = layer["bytes"]
+            path = os.path.join(self.data_dir, CKPT_NAME)
+            manifest = ckptmod.dump_manifest(at, layers)
+            written += await loop.run_in_executor(
+                None, lambda: _write_json_atomic(
+                    path, manifest, separators=(",", ":")))
+        except BaseException:
+            # nothing was published: these keys are still unsaved
+            self._dirty |= captured
+            raise
+        if kind == "base":
+            # a base written over a name that waits for deletion is live
+            self._ckpt_garbage = [n for n in self._ckpt_garbage
+                                  if n != layers[0]["name"]]
+        self._layers = layers
+        self._last_ckpt_bytes = written
+        self._last_ckpt_dirty = len(captured)
+        self._last_ckpt_records = len(items)
+
+    def _compaction_due(self) -> bool:
+        layers = self._layers
+        if len(layers) < 2:
+            return False
+        return len(layers) > ckptmod.MAX_LAYERS or \
+            sum(layer["bytes"] for layer in layers[1:]) >= layers[0]["bytes"]
+
+    async def _compact(self) -> None:
+        """Merge the layer FILES into one new base in the executor and
+        publish a manifest that names only it.  Runs under
+        ``_ckpt_running``; writes that arrive meanwhile are in the dirty
+        set and go into the next delta.  Merging once the deltas reach
+        the base's size keeps layer bytes written amortized O(1) per
+        WAL byte."""
+        loop = asyncio.get_running_loop()
+        names = [layer["name"] for layer in self._layers]
+        data_dir, at = self.data_dir, self.ckpt_lsn
+        base = await loop.run_in_executor(
+            None, lambda: ckptmod.merge_layers_offloaded(data_dir, names))
+        path = os.path.join(data_dir, CKPT_NAME)
+        await loop.run_in_executor(
+            None, lambda: _write_json_atomic(
+                path, ckptmod.dump_manifest(at, [base]),
+                separators=(",", ":")))
+        self._layers = [base]
+        await loop.run_in_executor(None, self._retire_layers, names)
+        self._compact_count += 1
+        self.log.debug("checkpoint layers compacted", merged=len(names),
+                       base=base["name"], bytes=base["bytes"])
+
+    def _retire_layers(self, superseded: List[str]) -> None:
+        """Deferred deletion.  A snapshot on the ``dir`` provider is a
+        tar of the LIVE directory, so a copy can pair the previous
+        manifest with the current files.  What the publication before
+        this one superseded is unlinked now; what this one supersedes
+        waits for the next.  Between such publications layers are only
+        ever added.  Called in the executor, under ``_ckpt_running``:
+        unlinking a large file takes the file system a while."""
+        live = {layer["name"] for layer in self._layers}
+        ckptmod.unlink_layers(self.data_dir,
+                              [n for n in self._ckpt_garbage
+                               if n not in live])
+        self._ckpt_garbage = [n for n in superseded if n not in live]
+
+    def checkpoint_info(self) -> dict:
+        """The ``ckpt`` query: what the checkpointer has on disk and what
+        it has done since start."""
+        return {
+            "ok": True,
+            "mode": self.settings.ckpt_mode,
+            "lsn": lsnmod.format_lsn(self.ckpt_lsn),
+            "layers": [dict(layer, lsn=lsnmod.format_lsn(layer["lsn"]))
+                       for layer in self._layers],
+            "dirty_keys": len(self._dirty),
+            "last_checkpoint_bytes": self._last_ckpt_bytes,
+            "last_checkpoint_dirty": self._last_ckpt_dirty,
+            "last_checkpoint_records": self._last_ckpt_records,
+            "checkpoints": self._ckpt_count,
+            "compactions": self._compact_count,
+        }
 
     # -------------------------------------------------------------- replay
     def _apply_op(self, op: dict) -> None:
         kind = op.get("op")
         if kind == "put":
             self.kv[op["k"]] = op["v"]
+            self._dirty.add(op["k"])
         elif kind == "del":
             self.kv.pop(op["k"], None)
+            self._dirty.add(op["k"])
         elif kind == "batch":
             for sub in op.get("ops") or []:
                 self._apply_op(sub)

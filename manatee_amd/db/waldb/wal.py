@@ -342,6 +342,15 @@ def _scan(buf: bytes) -> Tuple[int, List[Tuple[int, int]]]:
     return pos, records
 
 
+def encode_frame(payload: bytes) -> bytes:
+    """One WAL-format frame around ``payload`` — for record streams
+    outside the WAL proper (checkpoint layer files).  Native-accelerated."""
+    native = _codec()
+    if native is not None:
+        return native.encode_frame(payload)
+    return _HDR.pack(len(payload), zlib.crc32(payload)) + payload
+
+
 def parse_frames(data: bytes) -> Iterator[Tuple[int, bytes]]:
     """Split a raw replicated chunk into (frame_len, payload) records.
     The chunk always contains whole frames (senders send record-aligned).

@@ -59,7 +59,8 @@ def build_engine(mgr_cfg: dict, ip: str, pg_port: int, peer_name: str,
                  data_dir: str, log: Logger, store=None):
     kind = mgr_cfg.get("engine", "waldb")
     if kind == "waldb":
-        return WaldbEngine(data_dir, ip, pg_port, peer_name, log=log)
+        return WaldbEngine(data_dir, ip, pg_port, peer_name, log=log,
+                           tunables=mgr_cfg.get("waldbTunables"))
     if kind == "postgres":
         from .db.postgres import PostgresEngine
         from .storage.zfsstore import ZfsStore

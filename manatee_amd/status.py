@@ -123,6 +123,22 @@ class StatusServer:
                               labels)
             except Exception:
                 pass
+            info = getattr(db.engine, "checkpoint_info", None)
+            if info is not None:
+                try:
+                    ck = await info()
+                    gauge("manatee_checkpoint_dirty_keys", ck["dirty_keys"],
+                          "keys touched since the last checkpoint")
+                    gauge("manatee_checkpoint_last_bytes",
+                          ck["last_checkpoint_bytes"],
+                          "bytes the last checkpoint wrote")
+                    gauge("manatee_checkpoints", ck["checkpoints"],
+                          "checkpoints since the database started")
+                    gauge("manatee_checkpoint_compactions",
+                          ck["compactions"],
+                          "layer compactions since the database started")
+                except Exception:
+                    pass
         if db is not None and db.restore_client is not None:
             ro = db.restore_client.restore_object
             gauge("manatee_restore_active", int(ro.active),

@@ -115,6 +115,8 @@ class DevPeer:
             cfg["defaultVersion"] = c.pg_version
             cfg["pgBaseDir"] = c.pg_base_dir
             cfg["dbUser"] = "postgres"
+        if c.waldb_tunables:
+            out["postgresMgrCfg"]["waldbTunables"] = dict(c.waldb_tunables)
         return out
 
     def backupserver_config(self) -> dict:
@@ -352,8 +354,11 @@ class DevCluster:
                  storage_provider: str = "dir",
                  pg_version: str = "12",
                  zk_ensemble: int = 1,
-                 zk_election_timeout_ms: tuple = (500, 1000)):
+                 zk_election_timeout_ms: tuple = (500, 1000),
+                 waldb_tunables: Optional[dict] = None):
         self.base_dir = os.path.abspath(base_dir)
+        # waldb conf knobs for every peer (postgresMgrCfg.waldbTunables)
+        self.waldb_tunables = dict(waldb_tunables or {})
         self.ip = ip
         self.engine = engine
         self.shard_path = "/manatee/" + shard_name
@@ -825,13 +830,20 @@ def main(argv=None) -> int:
     ap.add_argument("--zk-ensemble", type=int, default=1,
                     help="coordination members (1 = standalone server, "
                          "3 = replicated ensemble)")
+    ap.add_argument("--checkpoint-mode", choices=("full", "incremental"),
+                    default=None,
+                    help="waldb checkpoint_mode for every peer "
+                         "(default: the engine's, full)")
     ns = ap.parse_args(argv)
 
     async def run():
         c = DevCluster(ns.dir, n_peers=ns.peers, shard_name=ns.shard,
                        singleton=ns.singleton or ns.peers == 1,
                        session_timeout_ms=ns.session_timeout_ms,
-                       zk_ensemble=ns.zk_ensemble)
+                       zk_ensemble=ns.zk_ensemble,
+                       waldb_tunables=(
+                           {"checkpoint_mode": ns.checkpoint_mode}
+                           if ns.checkpoint_mode else None))
         await c.start()
         print("zk:     %s" % c.zk_conn_str)
         print("shard:  %s" % c.shard_path)

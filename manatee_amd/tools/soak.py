@@ -202,10 +202,13 @@ ZK_ENSEMBLE_ACTIONS = ["kill_zk_leader", "kill_zk_follower"]
 
 async def soak(minutes: float, seed: int, workdir: str,
                cycles: Optional[int] = None,
-               engine: str = "waldb", zk_ensemble: int = 1) -> dict:
+               engine: str = "waldb", zk_ensemble: int = 1,
+               checkpoint_mode: Optional[str] = None) -> dict:
     rng = random.Random(seed)
     c = DevCluster(workdir, n_peers=3, shard_name="1.soak", proxied=True,
-                   engine=engine, zk_ensemble=zk_ensemble)
+                   engine=engine, zk_ensemble=zk_ensemble,
+                   waldb_tunables=({"checkpoint_mode": checkpoint_mode}
+                                   if checkpoint_mode else None))
     stats = {"cycles": 0, "kills": {}, "lost": 0, "acked": 0,
              "max_failover_s": 0.0, "failures": []}
     actions = list(ACTIONS)
@@ -382,13 +385,18 @@ def main(argv=None) -> int:
     ap.add_argument("--zk-ensemble", type=int, default=1,
                     help="coordination members; above 1 adds the "
                          "kill_zk_leader / kill_zk_follower faults")
+    ap.add_argument("--checkpoint-mode", choices=("full", "incremental"),
+                    default=None,
+                    help="waldb engine only: checkpoint_mode for every "
+                         "peer (default: the engine's, full)")
     ap.add_argument("-d", "--dir", default=None)
     ns = ap.parse_args(argv)
     workdir = ns.dir or tempfile.mkdtemp(prefix="manatee-soak-")
     try:
         stats = asyncio.run(soak(ns.minutes, ns.seed, workdir,
                                  cycles=ns.cycles, engine=ns.engine,
-                                 zk_ensemble=ns.zk_ensemble))
+                                 zk_ensemble=ns.zk_ensemble,
+                                 checkpoint_mode=ns.checkpoint_mode))
     finally:
         if ns.dir is None:
             shutil.rmtree(workdir, ignore_errors=True)
@@ -397,6 +405,8 @@ def main(argv=None) -> int:
     stats["engine"] = ns.engine
     if ns.zk_ensemble > 1:
         stats["zk_ensemble"] = ns.zk_ensemble
+    if ns.checkpoint_mode:
+        stats["checkpoint_mode"] = ns.checkpoint_mode
     print(json.dumps(stats))
     return 0 if ok else 1
 
