@@ -34,6 +34,7 @@ from . import ckpt as ckptmod
 from .ckpt import CheckpointCorrupt, CheckpointFormatError  # noqa: F401
 from .wal import (DEFAULT_SEGMENT_BYTES, Wal, WalGone, _codec, encode_op,
                   decode_op, parse_frames)
+from .wal import fsync_dir as _fsync_dir
 
 CONF_NAME = "waldb.conf"
 IDENT_NAME = "waldb_ident.json"
@@ -1059,7 +1060,10 @@ class ReplCore:
 
 
 def _write_json_atomic(path: str, obj, **dump_kw) -> int:
-    """tmp + fsync + rename: readers see the old file or the new one.
+    """tmp + fsync + rename + directory fsync: readers see the old file
+    or the new one, and once this returns a power loss cannot bring the
+    old one back (what is deleted next — WAL below a checkpoint, layers
+    a manifest superseded, the promote trigger — relies on that).
     Returns the size written."""
     tmp = path + ".tmp"
     with open(tmp, "w") as f:
@@ -1068,6 +1072,7 @@ def _write_json_atomic(path: str, obj, **dump_kw) -> int:
         os.fsync(f.fileno())
         size = os.fstat(f.fileno()).st_size
     os.replace(tmp, path)
+    _fsync_dir(os.path.dirname(path))
     return size
 
 

@@ -13,6 +13,10 @@ checkpoint + WAL-recycling discipline.  Only the LAST segment can have
 a torn tail (partial frame / bad crc), which is truncated on open —
 the expected state after ``kill -9`` (the only way this system ever
 stops a database; ref lib/postgresMgr.js:1484-1541 and MANATEE-188).
+Segments must abut: every file operation here is ordered so that a crash
+leaves a contiguous stream, and ``open`` refuses a directory with a hole
+rather than replaying across it.  A segment's directory entry is fsynced
+when the file is created, so WAL fsynced into it survives a power loss.
 
 ``start`` is the lowest LSN still on disk; a replica asking for older
 WAL must fall back to a full restore (``wal-gone``), exactly like a
@@ -49,6 +53,16 @@ LEGACY_NAME = "wal.log"          # pre-segmentation single-file layout
 
 def _seg_name(start: int) -> str:
     return "wal-%016x.seg" % start
+
+
+def fsync_dir(path: str) -> None:
+    """Make the directory's entries durable: a file that was created,
+    renamed or unlinked in it is only as durable as the directory."""
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        os.fsync(fd)
+    finally:
+        os.close(fd)
 
 
 class Wal:
@@ -94,9 +108,8 @@ class Wal:
             os.rename(legacy, self._seg_path(0))
         self._segs = self._list_segments()
         if not self._segs:
+            self._create_segment(replay_from)
             self._segs = [replay_from]
-            with open(self._seg_path(replay_from), "wb"):
-                pass
         self.start = self._segs[0]
         # validate + replay from the segment containing replay_from
         pos = self.start
@@ -104,6 +117,12 @@ class Wal:
         for i, seg_start in enumerate(self._segs):
             is_last = i == len(self._segs) - 1
             path = self._seg_path(seg_start)
+            if seg_start != end:
+                # a hole (or an overlap) in the stream: replaying across
+                # it would silently skip history
+                raise IOError(
+                    "corrupt WAL: segment %s starts at %d, but the "
+                    "segments before it end at %d" % (path, seg_start, end))
             size = os.path.getsize(path)
             if not is_last and seg_start + size <= replay_from:
                 end = seg_start + size
@@ -133,6 +152,13 @@ class Wal:
         self._open_active()
         return self.end
 
+    def _create_segment(self, start: int) -> None:
+        """An empty segment file whose directory entry is durable: WAL
+        fsynced into it later must not vanish with its name."""
+        with open(self._seg_path(start), "wb"):
+            pass
+        fsync_dir(self.dir)
+
     def _open_active(self) -> None:
         if self._fd is not None:
             os.close(self._fd)
@@ -151,9 +177,8 @@ class Wal:
         if self.end - self._active_start >= self.segment_bytes:
             self.flush_buffer()
             os.fsync(self._fd)
+            self._create_segment(self.end)
             self._segs.append(self.end)
-            with open(self._seg_path(self.end), "wb"):
-                pass
             self._open_active()
 
     def flush_buffer(self) -> None:
@@ -209,19 +234,29 @@ class Wal:
 
     # -------------------------------------------------------- truncation
     def truncate_to(self, lsn: int) -> None:
-        """Timeline fencing: discard everything above ``lsn``."""
+        """Timeline fencing: discard everything above ``lsn``.
+
+        Whole segments go newest first and the segment that holds
+        ``lsn`` is shortened last, so that a crash at any point leaves a
+        contiguous log — possibly more of it than asked for, never one
+        with a hole.  The unlinks are made durable before the
+        shortening: a dropped segment that came back after a power loss
+        would not abut the shortened one."""
         self.flush_buffer()
         keep = [s for s in self._segs if s <= lsn]
         drop = [s for s in self._segs if s > lsn]
-        for s in drop:
+        for s in reversed(drop):
             os.unlink(self._seg_path(s))
+            self._segs.remove(s)
+        if drop:
+            fsync_dir(self.dir)
         if not keep:
+            self._create_segment(lsn)
             keep = [lsn]
-            with open(self._seg_path(lsn), "wb"):
-                pass
         self._segs = keep
         self._open_active()
         os.ftruncate(self._fd, max(0, lsn - self._active_start))
+        os.fsync(self._fd)
         self.end = lsn
         self.start = self._segs[0]
 
