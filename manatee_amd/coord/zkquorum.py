@@ -18,6 +18,10 @@ clock or counter, so the replicas stay byte-identical (``dump_full()``).
 
 Sessions are replicated; their liveness is known to the leader only, and
 a new leader restarts every session's clock at one full timeout.
+With ``disconnect_grace_ms`` set, the serving leader also expires a
+session whose client closed its connection (FIN or RST) and did not
+re-attach within the grace; that observation is leader-local, never
+logged or snapshotted, and a new leader starts without it.
 Watches belong to a connection and die with it; a reconnecting client
 re-arms them with SetWatches and its last seen zxid, and whatever it
 missed fires at once.
@@ -300,10 +304,12 @@ class ZkQuorumServer(ZkServer):
                  snapshot_entries: int = 1000,
                  log: Optional[Logger] = None,
                  min_session_timeout_ms: int = 1000,
-                 max_session_timeout_ms: int = 120000):
+                 max_session_timeout_ms: int = 120000,
+                 disconnect_grace_ms: Optional[int] = None):
         super().__init__(host=client_host, port=client_port, log=log,
                          min_session_timeout_ms=min_session_timeout_ms,
-                         max_session_timeout_ms=max_session_timeout_ms)
+                         max_session_timeout_ms=max_session_timeout_ms,
+                         disconnect_grace_ms=disconnect_grace_ms)
         if not peers or server_id not in peers:
             raise ValueError("peers must list every member, this one "
                              "included")
@@ -564,11 +570,13 @@ class ZkQuorumServer(ZkServer):
     def _begin_serving(self, epoch: int) -> None:
         # everything up to this epoch's no-op is applied: no client has
         # seen a zxid this member does not have.  Liveness was the old
-        # leader's knowledge — every session gets one full timeout.
+        # leader's knowledge — every session gets one full timeout, and
+        # this member has seen no client close anything.
         now = time.monotonic()
         for sess in self.sessions.values():
             sess.last_seen = now
             sess.conn = None
+            sess.detached_at = None
         self._closing_sids.clear()
         self._last_zxid_assigned = self.zxid
         self._serving_epoch = epoch
@@ -914,6 +922,7 @@ class ZkQuorumServer(ZkServer):
                 except Exception:
                     pass
             sess.conn = writer
+            sess.detached_at = None
             sess.last_seen = time.monotonic()
             writer.write(jute.encode_connect_response(
                 sess.timeout_ms, sess.sid, sess.passwd))
@@ -961,6 +970,15 @@ class ZkQuorumServer(ZkServer):
                 # belonged to this connection and go with it
                 sess.conn = None
                 self._forget_watches(sess.sid)
+                # ... or until the disconnect grace, when it was the
+                # CLIENT that closed.  A leader that was deposed or is
+                # stopping aborted the connection itself, which says
+                # nothing about the client.
+                if not sess.closed and sess.sid not in self._closing_sids \
+                        and self._running and self.serving \
+                        and self._serving_epoch == epoch \
+                        and self._peer_closed(reader):
+                    self._mark_detached(sess)
             try:
                 writer.transport.abort()
             except Exception:
@@ -1087,16 +1105,23 @@ class ZkQuorumServer(ZkServer):
                     break
                 if sess.closed or sess.sid in self._closing_sids:
                     continue
-                if (now - sess.last_seen) * 1000.0 <= sess.timeout_ms:
+                if (now - sess.last_seen) * 1000.0 > sess.timeout_ms:
+                    self.log.info("session expired", sid="0x%x" % sess.sid,
+                                  timeout_ms=sess.timeout_ms)
+                    on_disconnect = False
+                elif self._grace_elapsed(sess, now):
+                    self._log_disconnect_expiry(sess, now)
+                    on_disconnect = True
+                else:
                     continue
-                self.log.info("session expired", sid="0x%x" % sess.sid,
-                              timeout_ms=sess.timeout_ms)
                 self._closing_sids.add(sess.sid)
                 sid = sess.sid
                 try:
                     await self._submit(lambda zxid, _now, sid=sid: {
                         "op": "session_close", "zxid": zxid, "sid": sid})
                     self.stats["expired_sessions"] += 1
+                    if on_disconnect:
+                        self.stats["expired_on_disconnect"] += 1
                 except _NotServing:
                     break
                 except Exception as exc:
@@ -1160,6 +1185,11 @@ def main(argv=None) -> int:
                     metavar="MIN,MAX")
     ap.add_argument("--heartbeat-ms", type=int, default=100)
     ap.add_argument("--snapshot-entries", type=int, default=1000)
+    ap.add_argument("--disconnect-grace-ms", type=int, default=None,
+                    metavar="MS",
+                    help="as leader, expire a session this long after its "
+                         "client closed the connection without "
+                         "re-attaching (default: off)")
     ap.add_argument("-v", "--verbose", action="count", default=0)
     ns = ap.parse_args(argv)
     log = _Logger("manatee-zkquorum", level=level_from_verbosity(ns.verbose))
@@ -1170,7 +1200,8 @@ def main(argv=None) -> int:
         peers=parse_peers(ns.peers), data_dir=ns.data_dir,
         election_timeout_ms=(int(lo), int(hi or lo)),
         heartbeat_ms=ns.heartbeat_ms,
-        snapshot_entries=ns.snapshot_entries, log=log)
+        snapshot_entries=ns.snapshot_entries, log=log,
+        disconnect_grace_ms=ns.disconnect_grace_ms)
     try:
         return asyncio.run(run_member(srv))
     except KeyboardInterrupt:

@@ -73,7 +73,7 @@ class _Node:
 
 class _Session:
     __slots__ = ("sid", "passwd", "timeout_ms", "last_seen", "ephemerals",
-                 "conn", "closed")
+                 "conn", "closed", "detached_at")
 
     def __init__(self, sid: int, passwd: bytes, timeout_ms: int):
         self.sid = sid
@@ -83,6 +83,10 @@ class _Session:
         self.ephemerals: Set[str] = set()
         self.conn: Optional[asyncio.StreamWriter] = None
         self.closed = False
+        # monotonic time at which the CLIENT's side closed the session's
+        # connection; None while attached, after silence without a close,
+        # or when this server dropped the connection itself
+        self.detached_at: Optional[float] = None
 
 
 _TRAILING_SEQ = re.compile(r"(\d{10})$")
@@ -108,7 +112,8 @@ class ZkServer:
                  tick_ms: int = 200,
                  min_session_timeout_ms: int = 1000,
                  max_session_timeout_ms: int = 120000,
-                 journal_path: Optional[str] = None):
+                 journal_path: Optional[str] = None,
+                 disconnect_grace_ms: Optional[int] = None):
         self.host = host
         self.port = port
         self.log = (log or null_logger()).child(component="ZkServer")
@@ -116,6 +121,12 @@ class ZkServer:
         self.min_to = min_session_timeout_ms
         self.max_to = max_session_timeout_ms
         self.journal_path = journal_path
+        # opt-in: a session whose client closed its connection (FIN/RST)
+        # and did not re-attach within this long is expired then, not at
+        # its timeout.  None or <= 0 is off; silence never counts.
+        self.disconnect_grace_ms = disconnect_grace_ms \
+            if disconnect_grace_ms and disconnect_grace_ms > 0 else None
+        self._stopping = False
         self._journal = None
         self._journal_entries = 0
         self.journal_compact_entries = 5000
@@ -128,7 +139,8 @@ class ZkServer:
         self.child_watches: Dict[str, Set[int]] = {}
         self._server: Optional[asyncio.AbstractServer] = None
         self._sweeper: Optional[asyncio.Task] = None
-        self.stats = {"requests": 0, "watch_events": 0, "expired_sessions": 0}
+        self.stats = {"requests": 0, "watch_events": 0, "expired_sessions": 0,
+                      "expired_on_disconnect": 0}
 
     # ------------------------------------------------------------ lifecycle
     async def start(self) -> None:
@@ -144,6 +156,7 @@ class ZkServer:
         self.log.info("zk server listening", host=self.host, port=self.port)
 
     async def stop(self) -> None:
+        self._stopping = True
         if self._sweeper:
             self._sweeper.cancel()
             try:
@@ -262,6 +275,23 @@ class ZkServer:
                                   timeout_ms=sess.timeout_ms)
                     self.stats["expired_sessions"] += 1
                     self._expire_session(sess)
+                elif self._grace_elapsed(sess, now):
+                    self._log_disconnect_expiry(sess, now)
+                    self.stats["expired_on_disconnect"] += 1
+                    self.stats["expired_sessions"] += 1
+                    self._expire_session(sess)
+
+    def _grace_elapsed(self, sess: _Session, now: float) -> bool:
+        return self.disconnect_grace_ms is not None and \
+            sess.detached_at is not None and \
+            (now - sess.detached_at) * 1000.0 > self.disconnect_grace_ms
+
+    def _log_disconnect_expiry(self, sess: _Session, now: float) -> None:
+        self.log.info("session expired after disconnect",
+                      sid="0x%x" % sess.sid,
+                      grace_ms=self.disconnect_grace_ms,
+                      detached_ms=int((now - sess.detached_at) * 1000.0),
+                      timeout_ms=sess.timeout_ms)
 
     def _expire_session(self, sess: _Session) -> None:
         sess.closed = True
@@ -426,15 +456,28 @@ class ZkServer:
     async def _read_frame(self, reader: asyncio.StreamReader) -> Optional[bytes]:
         try:
             hdr = await reader.readexactly(4)
-        except (asyncio.IncompleteReadError, ConnectionError):
+        except (asyncio.IncompleteReadError, ConnectionError, OSError):
             return None
         (n,) = struct.unpack(">i", hdr)
         if n < 0 or n > 8 * 1024 * 1024:
             return None
         try:
             return await reader.readexactly(n)
-        except (asyncio.IncompleteReadError, ConnectionError):
+        except (asyncio.IncompleteReadError, ConnectionError, OSError):
             return None
+
+    @staticmethod
+    def _peer_closed(reader: asyncio.StreamReader) -> bool:
+        """The stream ended (FIN) or failed (RST, or an error the kernel
+        reported) — as opposed to a handler that stopped reading on its
+        own.  A transport this server closed itself ends the stream too;
+        callers rule that out by ``sess.conn is writer`` and their own
+        stopping/serving state."""
+        return reader.at_eof() or reader.exception() is not None
+
+    def _mark_detached(self, sess: _Session) -> None:
+        if self.disconnect_grace_ms is not None:
+            sess.detached_at = time.monotonic()
 
     async def _handle_conn(self, reader: asyncio.StreamReader,
                            writer: asyncio.StreamWriter) -> None:
@@ -454,6 +497,7 @@ class ZkServer:
                         except Exception:
                             pass
                     sess.conn = writer
+                    sess.detached_at = None
                     sess.last_seen = time.monotonic()
                     writer.write(jute.encode_connect_response(
                         sess.timeout_ms, sess.sid, sess.passwd))
@@ -511,7 +555,14 @@ class ZkServer:
             self.log.error("connection handler error", err=exc)
         finally:
             if sess is not None and sess.conn is writer:
-                sess.conn = None  # session stays until timeout (disconnect != expiry)
+                # the session stays until its timeout (disconnect !=
+                # expiry) — unless the CLIENT closed and the disconnect
+                # grace is on: then the sweeper gives it that long to
+                # re-attach.  A close or abort of our own proves nothing.
+                sess.conn = None
+                if not sess.closed and not self._stopping and \
+                        self._peer_closed(reader):
+                    self._mark_detached(sess)
             try:
                 writer.close()
             except Exception:
@@ -635,8 +686,10 @@ class ZkServer:
 
 
 async def run_standalone(host: str, port: int, log: Logger,
-                         journal_path: Optional[str] = None) -> None:
-    srv = ZkServer(host=host, port=port, log=log, journal_path=journal_path)
+                         journal_path: Optional[str] = None,
+                         disconnect_grace_ms: Optional[int] = None) -> None:
+    srv = ZkServer(host=host, port=port, log=log, journal_path=journal_path,
+                   disconnect_grace_ms=disconnect_grace_ms)
     await srv.start()
     try:
         while True:
@@ -653,12 +706,18 @@ def main(argv=None) -> int:
     ap.add_argument("-H", "--host", default="127.0.0.1")
     ap.add_argument("-p", "--port", type=int, default=2181)
     ap.add_argument("-j", "--journal", default=None)
+    ap.add_argument("-g", "--disconnect-grace-ms", type=int, default=None,
+                    metavar="MS",
+                    help="expire a session this long after its client "
+                         "closed the connection without re-attaching "
+                         "(default: off, the session timeout alone decides)")
     ap.add_argument("-v", "--verbose", action="count", default=0)
     ns = ap.parse_args(argv)
     log = _Logger("manatee-zk", level=level_from_verbosity(ns.verbose))
     try:
-        asyncio.run(run_standalone(ns.host, ns.port, log,
-                                   journal_path=ns.journal))
+        asyncio.run(run_standalone(
+            ns.host, ns.port, log, journal_path=ns.journal,
+            disconnect_grace_ms=ns.disconnect_grace_ms))
     except KeyboardInterrupt:
         pass
     return 0

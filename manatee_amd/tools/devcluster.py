@@ -355,7 +355,8 @@ class DevCluster:
                  pg_version: str = "12",
                  zk_ensemble: int = 1,
                  zk_election_timeout_ms: tuple = (500, 1000),
-                 waldb_tunables: Optional[dict] = None):
+                 waldb_tunables: Optional[dict] = None,
+                 zk_disconnect_grace_ms: Optional[int] = None):
         self.base_dir = os.path.abspath(base_dir)
         # waldb conf knobs for every peer (postgresMgrCfg.waldbTunables)
         self.waldb_tunables = dict(waldb_tunables or {})
@@ -363,6 +364,15 @@ class DevCluster:
         self.engine = engine
         self.shard_path = "/manatee/" + shard_name
         self.session_timeout_ms = session_timeout_ms
+        # coordination servers' disconnect grace (coord/zkserver); when
+        # not given, MANATEE_ZK_DISCONNECT_GRACE_MS decides, unset = off
+        if zk_disconnect_grace_ms is None:
+            env_grace = os.environ.get("MANATEE_ZK_DISCONNECT_GRACE_MS")
+            if env_grace:
+                zk_disconnect_grace_ms = int(env_grace)
+        self.zk_disconnect_grace_ms = zk_disconnect_grace_ms \
+            if zk_disconnect_grace_ms and zk_disconnect_grace_ms > 0 \
+            else None
         self.health_interval_ms = health_interval_ms
         self.health_timeout_ms = health_timeout_ms
         self.ops_timeout_ms = ops_timeout_ms
@@ -479,8 +489,14 @@ class DevCluster:
         self.zk_proc = subprocess.Popen(
             [sys.executable, "-m", "manatee_amd.coord.zkserver",
              "-H", self.ip, "-p", str(self.zk_port),
-             "-j", os.path.join(self.base_dir, "zk-journal.jsonl")],
+             "-j", os.path.join(self.base_dir, "zk-journal.jsonl")]
+            + self._zk_grace_args(),
             env=env, stdout=logf, stderr=logf, start_new_session=True)
+
+    def _zk_grace_args(self) -> List[str]:
+        if self.zk_disconnect_grace_ms is None:
+            return []
+        return ["--disconnect-grace-ms", str(self.zk_disconnect_grace_ms)]
 
     def kill_zk(self) -> None:
         """SIGKILL the coordination server (full-ZK outage tier of the
@@ -530,7 +546,8 @@ class DevCluster:
              "--client", "%s:%d" % (self.ip, m["client_port"]),
              "--peers", peers, "--data-dir", m["dir"],
              "--election-timeout-ms",
-             "%d,%d" % self.zk_election_timeout_ms, "-v"],
+             "%d,%d" % self.zk_election_timeout_ms, "-v"]
+            + self._zk_grace_args(),
             env=env, stdout=logf, stderr=logf, start_new_session=True)
 
     def kill_zk_member(self, i: int) -> None:
@@ -830,6 +847,11 @@ def main(argv=None) -> int:
     ap.add_argument("--zk-ensemble", type=int, default=1,
                     help="coordination members (1 = standalone server, "
                          "3 = replicated ensemble)")
+    ap.add_argument("--zk-disconnect-grace-ms", type=int, default=None,
+                    metavar="MS",
+                    help="coordination servers expire a session this long "
+                         "after its client closed the connection (default: "
+                         "$MANATEE_ZK_DISCONNECT_GRACE_MS, else off)")
     ap.add_argument("--checkpoint-mode", choices=("full", "incremental"),
                     default=None,
                     help="waldb checkpoint_mode for every peer "
@@ -841,6 +863,7 @@ def main(argv=None) -> int:
                        singleton=ns.singleton or ns.peers == 1,
                        session_timeout_ms=ns.session_timeout_ms,
                        zk_ensemble=ns.zk_ensemble,
+                       zk_disconnect_grace_ms=ns.zk_disconnect_grace_ms,
                        waldb_tunables=(
                            {"checkpoint_mode": ns.checkpoint_mode}
                            if ns.checkpoint_mode else None))

@@ -4,6 +4,7 @@ acknowledged-write loss after every cycle.
 
     python -m manatee_amd.tools.soak --minutes 10 [--cycles 50]
         [--seed 7] [-d DIR] [--zk-ensemble 3]
+        [--zk-disconnect-grace-ms 500]
 
 Faults drawn each cycle: SIGKILL primary / sync / async, SIGKILL just
 the database child (sitter must restart it), SIGSTOP+SIGCONT the
@@ -203,10 +204,12 @@ ZK_ENSEMBLE_ACTIONS = ["kill_zk_leader", "kill_zk_follower"]
 async def soak(minutes: float, seed: int, workdir: str,
                cycles: Optional[int] = None,
                engine: str = "waldb", zk_ensemble: int = 1,
-               checkpoint_mode: Optional[str] = None) -> dict:
+               checkpoint_mode: Optional[str] = None,
+               zk_disconnect_grace_ms: Optional[int] = None) -> dict:
     rng = random.Random(seed)
     c = DevCluster(workdir, n_peers=3, shard_name="1.soak", proxied=True,
                    engine=engine, zk_ensemble=zk_ensemble,
+                   zk_disconnect_grace_ms=zk_disconnect_grace_ms,
                    waldb_tunables=({"checkpoint_mode": checkpoint_mode}
                                    if checkpoint_mode else None))
     stats = {"cycles": 0, "kills": {}, "lost": 0, "acked": 0,
@@ -385,6 +388,10 @@ def main(argv=None) -> int:
     ap.add_argument("--zk-ensemble", type=int, default=1,
                     help="coordination members; above 1 adds the "
                          "kill_zk_leader / kill_zk_follower faults")
+    ap.add_argument("--zk-disconnect-grace-ms", type=int, default=None,
+                    metavar="MS",
+                    help="run the coordination server(s) with this "
+                         "disconnect grace (default: off)")
     ap.add_argument("--checkpoint-mode", choices=("full", "incremental"),
                     default=None,
                     help="waldb engine only: checkpoint_mode for every "
@@ -396,7 +403,9 @@ def main(argv=None) -> int:
         stats = asyncio.run(soak(ns.minutes, ns.seed, workdir,
                                  cycles=ns.cycles, engine=ns.engine,
                                  zk_ensemble=ns.zk_ensemble,
-                                 checkpoint_mode=ns.checkpoint_mode))
+                                 checkpoint_mode=ns.checkpoint_mode,
+                                 zk_disconnect_grace_ms=(
+                                     ns.zk_disconnect_grace_ms)))
     finally:
         if ns.dir is None:
             shutil.rmtree(workdir, ignore_errors=True)
@@ -405,6 +414,8 @@ def main(argv=None) -> int:
     stats["engine"] = ns.engine
     if ns.zk_ensemble > 1:
         stats["zk_ensemble"] = ns.zk_ensemble
+    if ns.zk_disconnect_grace_ms:
+        stats["zk_disconnect_grace_ms"] = ns.zk_disconnect_grace_ms
     if ns.checkpoint_mode:
         stats["checkpoint_mode"] = ns.checkpoint_mode
     print(json.dumps(stats))
