@@ -25,6 +25,7 @@ import time
 from typing import List, Optional
 
 from .. import __version__
+from ..common import lsn as lsnmod
 from ..common.logging import null_logger
 from ..db.waldb.client import WaldbClient
 from ..fsm import state as st
@@ -605,7 +606,12 @@ async def cmd_rebuild(ns) -> int:
     refuse on the primary; require the peer's sitter to be stopped (its
     election ephemeral gone); isolate (or destroy, if deposed) the data
     store; remove the peer from the deposed list; restart the sitter
-    (via --start-cmd) and watch the restore until the peer rejoins."""
+    (via --start-cmd) and watch the restore until the peer rejoins.
+
+    ``--rewind`` keeps the store: the stopped database's WAL is cut back
+    to where it parts from the current primary's (db/waldb/rewind.py),
+    so the peer rejoins by streaming.  A rewind that refuses changes
+    nothing — not the store, not the deposed list — and exits non-zero."""
     cfg_path = ns.config or os.environ.get("MANATEE_SITTER_CONFIG")
     if not cfg_path:
         raise UsageError("rebuild requires -c/--config (or "
@@ -629,9 +635,10 @@ async def cmd_rebuild(ns) -> int:
         deposed = any(d.get("id") == peer_id
                       for d in state.get("deposed") or [])
         if not ns.yes:
-            return _fail("rebuild destroys this peer's local data%s; "
+            return _fail("rebuild %s this peer's local data%s; "
                          "confirm with -y"
-                         % (" (peer is DEPOSED)" if deposed else ""))
+                         % ("rewinds" if ns.rewind else "destroys",
+                            " (peer is DEPOSED)" if deposed else ""))
         if ns.stop_cmd:
             proc = await asyncio.create_subprocess_shell(ns.stop_cmd)
             await proc.wait()
@@ -650,7 +657,11 @@ async def cmd_rebuild(ns) -> int:
         # isolate or destroy the local store
         from ..storage import open_store
         store = open_store(store_cfg, log=null_logger())
-        if await store.exists():
+        if ns.rewind:
+            rc = await _rebuild_rewind(zk, shard, cfg, store, peer_id)
+            if rc:
+                return rc
+        elif await store.exists():
             if deposed:
                 await store.destroy()
                 print("destroyed local store (peer was deposed)")
@@ -665,7 +676,9 @@ async def cmd_rebuild(ns) -> int:
             except adm.AdmError:
                 pass
         if not ns.start_cmd:
-            print("local state cleared; restart the sitter to restore "
+            print("local state rewound; restart the sitter to rejoin"
+                  if ns.rewind else
+                  "local state cleared; restart the sitter to restore "
                   "from the primary")
             return 0
         proc = await asyncio.create_subprocess_shell(ns.start_cmd)
@@ -719,6 +732,48 @@ async def cmd_rebuild(ns) -> int:
             await asyncio.sleep(1.0)
         return _fail("peer did not rejoin within %ds" % ns.timeout)
     return await _with_zk(ns, go)
+
+
+async def _rebuild_rewind(zk, shard: str, cfg: dict, store,
+                          peer_id: str) -> int:
+    """``rebuild --rewind``: rewind this peer's stopped database against
+    the CURRENT primary.  0 if the WAL was cut (or needed no cut)."""
+    hint = "; rerun without --rewind to restore from the primary"
+    mgr_cfg = cfg["postgresMgrCfg"]
+    if mgr_cfg.get("engine", "waldb") != "waldb":
+        return _fail("rewind refused: unsupported by the %s engine%s"
+                     % (mgr_cfg.get("engine"), hint))
+    state, _ = await adm.get_state(zk, shard)
+    primary = (state or {}).get("primary") or {}
+    if not primary.get("pgUrl") or primary.get("id") == peer_id:
+        return _fail("rewind refused: no other primary in the cluster "
+                     "state" + hint)
+    from ..db.engine import url_to_hostport
+    from ..db.manager import leave_rewind_record
+    from ..db.waldb import rewind as rewindmod
+    host, port = url_to_hostport(primary["pgUrl"])
+    data_dir = mgr_cfg.get("dataDir") or \
+        os.path.join(store.mountpoint(), "data")
+    if not os.path.isdir(data_dir):
+        return _fail("rewind refused: no data directory at %s%s"
+                     % (data_dir, hint))
+    res = await asyncio.get_running_loop().run_in_executor(
+        None, rewindmod.rewind_data_dir, data_dir, host, port,
+        null_logger())
+    if not res.ok:
+        return _fail("rewind refused: %s%s" % (res.reason, hint))
+    if res.result == "noop":
+        print("rewind: noop, WAL ends at the fork point %s (0 bytes cut)"
+              % lsnmod.format_lsn(res.fork_lsn))
+    else:
+        print("rewound to the fork point %s (%d bytes cut%s)"
+              % (lsnmod.format_lsn(res.fork_lsn), res.bytes_cut,
+                 ", finished an interrupted rewind" if res.resumed else ""))
+    try:
+        leave_rewind_record(store, res.as_dict())
+    except OSError:
+        pass
+    return 0
 
 
 # --------------------------------------------------------------- plumbing
@@ -825,6 +880,9 @@ def _mk_parser() -> argparse.ArgumentParser:
     sp.add_argument("--start-cmd",
                     help="command to start the local sitter")
     sp.add_argument("--timeout", type=int, default=300)
+    sp.add_argument("--rewind", action="store_true",
+                    help="keep the store: cut the WAL back to the fork "
+                         "point instead of restoring (waldb engine)")
     return p
 
 

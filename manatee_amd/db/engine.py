@@ -88,6 +88,12 @@ class Engine:
         replay_lsn, caught_up}."""
         raise NotImplementedError
 
+    async def rewind(self, upstream_url: str) -> dict:
+        """Cut the STOPPED database's WAL back to where it and the
+        upstream part ways, instead of a restore.  Returns ``{ok,
+        result, reason, ...}``; an engine that cannot says so."""
+        return {"ok": False, "result": "refused", "reason": "unsupported"}
+
     async def close(self) -> None:
         pass
 
@@ -174,6 +180,16 @@ class WaldbEngine(Engine):
                                    "waldb.log"))
         except FileNotFoundError:
             pass
+
+    async def rewind(self, upstream_url: str) -> dict:
+        import asyncio
+        from .waldb import rewind as rewindmod
+        host, port = url_to_hostport(upstream_url)
+        await self.close()
+        res = await asyncio.get_running_loop().run_in_executor(
+            None, rewindmod.rewind_data_dir, self.data_dir, host, port,
+            self.log)
+        return res.as_dict()
 
     def spawn_argv(self) -> List[str]:
         return [sys.executable, "-m", "manatee_amd.db.waldb.server",

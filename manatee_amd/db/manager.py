@@ -33,6 +33,7 @@ Preserved behaviors (reference citations inline):
 from __future__ import annotations
 
 import asyncio
+import json
 import os
 import signal
 import time
@@ -44,6 +45,18 @@ from ..common import procutil
 from ..common.logging import Logger, null_logger
 from ..storage.provider import SnapshotStore
 from .engine import Engine, peer_id_from_urls
+
+
+# the result `manatee-adm rebuild --rewind` hands to the next sitter
+REWIND_RECORD = "rewind_last.json"
+
+
+def leave_rewind_record(store: SnapshotStore, result: dict) -> None:
+    """Operator side of ``REWIND_RECORD``: called with the sitter down,
+    after a rewind that succeeded."""
+    path = os.path.join(os.path.dirname(store.mountpoint()), REWIND_RECORD)
+    with open(path, "w") as f:
+        json.dump(result, f)
 
 
 def db_child_preexec() -> None:
@@ -74,6 +87,7 @@ class DbManager:
                  replication_timeout_s: float = 60.0,
                  repl_poll_s: float = 0.2,
                  one_node_write_mode: bool = False,
+                 rewind_on_divergence: bool = False,
                  log: Optional[Logger] = None):
         self.engine = engine
         self.store = store
@@ -84,6 +98,9 @@ class DbManager:
         self.replication_timeout_s = replication_timeout_s
         self.repl_poll_s = repl_poll_s
         self.one_node_write_mode = one_node_write_mode
+        # postgresMgrCfg.rewindOnDivergence: try the engine's rewind
+        # before a restore when a standby is refused as diverged
+        self.rewind_on_divergence = rewind_on_divergence
         self.log = (log or null_logger()).child(component="DbManager")
 
         self.healthy = False
@@ -99,6 +116,11 @@ class DbManager:
         self._applied: Optional[dict] = None
         self.restore_client: Optional[RestoreClient] = None
         self._closing = False
+        # last rewind {result, reason, ...} and counters for /metrics
+        self.last_rewind: Optional[dict] = None
+        self.rewinds_total: Dict[str, int] = {}
+        self.restores_total = 0
+        self._adopt_operator_rewind()
 
     # --------------------------------------------------------------- events
     def on(self, event: str, cb: Callable) -> None:
@@ -487,6 +509,11 @@ class DbManager:
             # during failover while the new primary restarts.
             verdict = await self._await_streaming(timeout_s=3.0)
             if verdict == "diverged":
+                # one attempt per transition; anything but a streaming
+                # standby afterwards falls through to the restore
+                if self.rewind_on_divergence and \
+                        await self._try_rewind(upstream):
+                    return
                 self.log.warn("WAL diverged from upstream; restoring")
                 need_restore = True
             elif verdict == "disconnected":
@@ -497,6 +524,65 @@ class DbManager:
                         self._standby_watch())
         if need_restore:
             await self._restore_and_start(upstream, restore_peer)
+
+    def _rewind_record_path(self) -> Optional[str]:
+        """Where ``manatee-adm rebuild --rewind`` leaves its result for
+        the next sitter: beside the dataset, like ``db_child.pid``."""
+        try:
+            return os.path.join(os.path.dirname(self.store.mountpoint()),
+                                REWIND_RECORD)
+        except Exception:
+            return None
+
+    def _adopt_operator_rewind(self) -> None:
+        """Count a rewind the operator ran while this sitter was down.
+        The record is consumed: it is counted once."""
+        path = self._rewind_record_path()
+        if path is None:
+            return
+        try:
+            with open(path) as f:
+                res = json.load(f)
+            os.unlink(path)
+        except (OSError, ValueError):
+            return
+        if isinstance(res, dict):
+            self._note_rewind(dict(res, by="manatee-adm"))
+
+    def _note_rewind(self, res: dict) -> None:
+        self.last_rewind = res
+        result = str(res.get("result") or "refused")
+        self.rewinds_total[result] = self.rewinds_total.get(result, 0) + 1
+
+    async def _try_rewind(self, upstream: dict) -> bool:
+        """Rewind the diverged database to the fork point and start it
+        again.  True only if it then streams from the upstream."""
+        await self._stop_db()
+        try:
+            res = await self.engine.rewind(upstream["pgUrl"])
+        except Exception as exc:
+            res = {"ok": False, "result": "refused",
+                   "reason": "error: %s" % (exc,)}
+        if not res.get("ok"):
+            self.log.warn("rewind refused", reason=res.get("reason"))
+            self._note_rewind(res)
+            return False
+        self.log.info("rewound to the fork point", result=res.get("result"),
+                      fork=res.get("fork_lsn"),
+                      bytes_cut=res.get("bytes_cut"))
+        try:
+            await self._start_db()
+            verdict = await self._await_streaming(timeout_s=3.0)
+        except Exception as exc:
+            verdict = "start failed: %s" % (exc,)
+        if verdict != "streaming":
+            self.log.warn("not streaming after the rewind",
+                          verdict=verdict)
+            self._note_rewind(dict(res, ok=False, result="failed",
+                                   reason="after rewind: %s" % verdict))
+            return False
+        self._note_rewind(res)
+        return True
 
     async def _standby_watch(self) -> None:
         """Background: if a standby that could not reach its upstream turns
@@ -545,6 +631,7 @@ class DbManager:
         """Full restore from the restore peer's backup server, then start
         as a standby (ref zfsClient.restore → _standby retry :1375-1448)."""
         await self._stop_db()
+        self.restores_total += 1
         self.restore_client = RestoreClient(self.store, self.ip,
                                             log=self.log)
         # ONE attempt per reconfigure, like the reference's _standby
@@ -591,4 +678,5 @@ class DbManager:
             "appliedConfig": self._applied,
             "restore": (self.restore_client.restore_object.as_dict()
                         if self.restore_client else None),
+            "rewind": self.last_rewind,
         }

@@ -25,12 +25,14 @@ import struct
 import sys
 import time
 import uuid
+import zlib
 from typing import Dict, Iterator, List, Optional, Tuple
 
 from ...common import dial
 from ...common import lsn as lsnmod
 from ...common.logging import Logger
 from . import ckpt as ckptmod
+from . import rewind as rewindmod
 from .ckpt import CheckpointCorrupt, CheckpointFormatError  # noqa: F401
 from .wal import (DEFAULT_SEGMENT_BYTES, Wal, WalGone, _codec, encode_op,
                   decode_op, parse_frames)
@@ -252,6 +254,14 @@ class ReplCore:
     # -------------------------------------------------------------- startup
     async def start(self) -> None:
         self._adopt(self.read_settings(self.settings))
+        if os.path.exists(os.path.join(self.data_dir,
+                                       rewindmod.MARKER_NAME)):
+            # a rewind was interrupted: WAL, checkpoint and ident may
+            # belong to different histories until it is finished
+            self.log.error("data directory holds an unfinished rewind; "
+                           "REFUSING to start (run the rewind again)",
+                           marker=rewindmod.MARKER_NAME)
+            raise rewindmod.RewindPending(rewindmod.MARKER_NAME)
         self.load_ident()
 
         # recover: checkpoint (if any) + WAL tail replay
@@ -828,6 +838,43 @@ class ReplCore:
             # it must bootstrap from a snapshot instead
             return "wal-gone"
         return None
+
+    async def rewind_probe(self, req: dict) -> dict:
+        """Answer a diverged peer that wants to rewind (``rewind.py``):
+        where its history and ours part ways, and the CRC-32 of our WAL
+        in the window just below that point, which it compares with its
+        own bytes.  Changes no state."""
+        if req.get("ident") != self.ident.get("ident"):
+            return {"ok": False, "error": "ident-mismatch"}
+        try:
+            _tl, fork = rewindmod.fork_point(
+                int(req.get("timeline", 0)), req.get("history") or [],
+                int(req["wal_end"]), self.timeline, self.history,
+                self.wal.end)
+            start = rewindmod.probe_window(int(req["wal_start"]),
+                                           self.wal.start, fork)
+        except (KeyError, TypeError, ValueError):
+            return {"ok": False, "error": "bad rewind-probe request"}
+        if start >= fork:
+            return {"ok": False, "error": "unverifiable"}
+        # a slice at a time: one CRC over the whole window would hold
+        # the event loop (and every commit ack) for its duration
+        crc, pos = 0, start
+        try:
+            while pos < fork:
+                data = self.wal.read(
+                    pos, min(rewindmod.CRC_CHUNK, fork - pos))
+                if not data:
+                    return {"ok": False, "error": "unverifiable"}
+                crc = zlib.crc32(data, crc)
+                pos += len(data)
+                await asyncio.sleep(0)
+        except WalGone:
+            # a checkpoint recycled the window while we were reading it
+            return {"ok": False, "error": "unverifiable"}
+        return {"ok": True, "timeline": self.timeline,
+                "history": self.history, "fork_lsn": fork,
+                "window_start": start, "crc32": crc}
 
     # ------------------------------------------------------ replication in
     async def _replication_client(self, gen: int) -> None:

@@ -93,6 +93,7 @@ class Shard:
             replication_timeout_s=mgr_cfg.get("replicationTimeout",
                                               60000) / 1000.0,
             one_node_write_mode=bool(mgr_cfg.get("oneNodeWriteMode")),
+            rewind_on_divergence=bool(mgr_cfg.get("rewindOnDivergence")),
             log=self.log)
 
         zk_cfg = cfg["zkCfg"]

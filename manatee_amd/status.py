@@ -139,6 +139,18 @@ class StatusServer:
                           "layer compactions since the database started")
                 except Exception:
                     pass
+        if db is not None:
+            lines.append("# HELP manatee_rewinds_total divergence "
+                         "recoveries attempted by WAL rewind, by result")
+            lines.append("# TYPE manatee_rewinds_total counter")
+            for result in sorted(set(db.rewinds_total)
+                                 | {"ok", "noop", "refused", "failed"}):
+                lines.append('manatee_rewinds_total{result="%s"} %d'
+                             % (result, db.rewinds_total.get(result, 0)))
+            lines.append("# HELP manatee_restores_total full restores "
+                         "started from a restore peer")
+            lines.append("# TYPE manatee_restores_total counter")
+            lines.append("manatee_restores_total %d" % db.restores_total)
         if db is not None and db.restore_client is not None:
             ro = db.restore_client.restore_object
             gauge("manatee_restore_active", int(ro.active),

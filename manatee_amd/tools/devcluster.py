@@ -49,6 +49,16 @@ def _ephemeral_low() -> int:
 _EPHEMERAL_LOW = _ephemeral_low()
 
 
+class RewindRefused(Exception):
+    """``rebuild_peer(rewind=True)``: the rewind refused; the peer's
+    store and the cluster state are as they were.  ``args[0]`` is the
+    reason, ``result`` the rewind's whole answer."""
+
+    def __init__(self, reason: str, result: Optional[dict] = None):
+        super().__init__(reason)
+        self.result = result
+
+
 class DevPeer:
     def __init__(self, cluster: "DevCluster", index: int, base_port: int):
         self.cluster = cluster
@@ -117,6 +127,8 @@ class DevPeer:
             cfg["dbUser"] = "postgres"
         if c.waldb_tunables:
             out["postgresMgrCfg"]["waldbTunables"] = dict(c.waldb_tunables)
+        if c.rewind_on_divergence:
+            out["postgresMgrCfg"]["rewindOnDivergence"] = True
         return out
 
     def backupserver_config(self) -> dict:
@@ -356,8 +368,11 @@ class DevCluster:
                  zk_ensemble: int = 1,
                  zk_election_timeout_ms: tuple = (500, 1000),
                  waldb_tunables: Optional[dict] = None,
-                 zk_disconnect_grace_ms: Optional[int] = None):
+                 zk_disconnect_grace_ms: Optional[int] = None,
+                 rewind_on_divergence: bool = False):
         self.base_dir = os.path.abspath(base_dir)
+        # postgresMgrCfg.rewindOnDivergence for every peer
+        self.rewind_on_divergence = rewind_on_divergence
         # waldb conf knobs for every peer (postgresMgrCfg.waldbTunables)
         self.waldb_tunables = dict(waldb_tunables or {})
         self.ip = ip
@@ -773,23 +788,50 @@ class DevCluster:
         raise KeyError(peer_id)
 
     async def rebuild_peer(self, peer: DevPeer,
-                           timeout_s: float = 120.0) -> None:
+                           timeout_s: float = 120.0,
+                           rewind: bool = False) -> Optional[dict]:
         """The ``manatee-adm rebuild`` flow for a dead/deposed peer
         (ref lib/adm.js:1319-1684): stop it, destroy its dataset (it is
         deposed — its WAL may have diverged), remove it from the deposed
         list, restart it; it restores from the primary and rejoins as an
-        async."""
+        async.
+
+        ``rewind=True`` is ``rebuild --rewind``: the dataset is kept and
+        its WAL cut back to where it parts from the primary's
+        (``db/waldb/rewind.py``).  Returns the rewind's result; a
+        refusal raises ``RewindRefused`` with nothing changed."""
         import shutil
         from ..adm import core as adm
         from ..storage import open_store
         peer.kill9()
-        # destroy through the provider (for zfs the pool state lives
-        # outside store_dir; ref deposed ⇒ destroyDataset lib/adm.js:1479)
-        try:
-            await open_store(peer.storage_cfg(), log=None).destroy()
-        except Exception:
-            pass
-        shutil.rmtree(peer.store_dir, ignore_errors=True)
+        result = None
+        if rewind:
+            from ..db.engine import url_to_hostport
+            from ..db.waldb import rewind as rewindmod
+            from ..common.logging import null_logger
+            state = await self.cluster_state()
+            if not state or state["primary"]["id"] == peer.id:
+                raise RewindRefused("no other primary to rewind against")
+            host, port = url_to_hostport(state["primary"]["pgUrl"])
+            store = open_store(peer.storage_cfg(), log=None)
+            data_dir = os.path.join(store.mountpoint(), "data")
+            res = await asyncio.get_running_loop().run_in_executor(
+                None, rewindmod.rewind_data_dir, data_dir, host, port,
+                null_logger())
+            result = res.as_dict()
+            if not res.ok:
+                raise RewindRefused(res.reason or "refused", result)
+            from ..db.manager import leave_rewind_record
+            leave_rewind_record(store, result)
+        else:
+            # destroy through the provider (for zfs the pool state lives
+            # outside store_dir; ref deposed ⇒ destroyDataset
+            # lib/adm.js:1479)
+            try:
+                await open_store(peer.storage_cfg(), log=None).destroy()
+            except Exception:
+                pass
+            shutil.rmtree(peer.store_dir, ignore_errors=True)
         zk = await adm.create_zk_client(self.zk_conn_str)
         try:
             state, version = await adm.get_state(zk, self.shard_path)
@@ -802,6 +844,7 @@ class DevCluster:
         await self.wait_cluster(
             lambda s: any(a["id"] == peer.id for a in s.get("async", [])),
             timeout_s=timeout_s, what="rebuilt peer rejoining as async")
+        return result
 
     async def wait_writable(self, timeout_s: float = 60.0) -> DevPeer:
         """Wait until the cluster primary accepts a write; returns it."""

@@ -35,7 +35,7 @@ import tempfile
 import time
 from typing import Optional
 
-from .devcluster import DevCluster
+from .devcluster import DevCluster, RewindRefused
 
 WINDOW = 4000
 BURST = 25
@@ -205,7 +205,8 @@ async def soak(minutes: float, seed: int, workdir: str,
                cycles: Optional[int] = None,
                engine: str = "waldb", zk_ensemble: int = 1,
                checkpoint_mode: Optional[str] = None,
-               zk_disconnect_grace_ms: Optional[int] = None) -> dict:
+               zk_disconnect_grace_ms: Optional[int] = None,
+               rebuild_mode: str = "restore") -> dict:
     rng = random.Random(seed)
     c = DevCluster(workdir, n_peers=3, shard_name="1.soak", proxied=True,
                    engine=engine, zk_ensemble=zk_ensemble,
@@ -214,6 +215,24 @@ async def soak(minutes: float, seed: int, workdir: str,
                                    if checkpoint_mode else None))
     stats = {"cycles": 0, "kills": {}, "lost": 0, "acked": 0,
              "max_failover_s": 0.0, "failures": []}
+    if rebuild_mode == "rewind":
+        stats["rebuild_mode"] = rebuild_mode
+        stats["rewinds"] = {}
+
+    async def rebuild(p) -> None:
+        """Heal a deposed peer: by rewind when asked to, by the full
+        restore when not, or when the rewind refuses."""
+        if rebuild_mode == "rewind":
+            try:
+                res = await c.rebuild_peer(p, timeout_s=120, rewind=True)
+                outcome = res["result"]
+            except RewindRefused as exc:
+                outcome = "refused: %s" % str(exc).split(":")[0]
+            stats["rewinds"][outcome] = \
+                stats["rewinds"].get(outcome, 0) + 1
+            if not outcome.startswith("refused"):
+                return
+        await c.rebuild_peer(p, timeout_s=120)
     actions = list(ACTIONS)
     if zk_ensemble > 1:
         actions += ZK_ENSEMBLE_ACTIONS
@@ -335,7 +354,7 @@ async def soak(minutes: float, seed: int, workdir: str,
                     await asyncio.sleep(2.0)
                     for p in c.peers:
                         if p.id in deposed:
-                            await c.rebuild_peer(p, timeout_s=120)
+                            await rebuild(p)
                     await c.wait_writable(timeout_s=120)
                 except Exception as exc:
                     stats["failures"].append("%s: %s" % (action, exc))
@@ -361,7 +380,7 @@ async def soak(minutes: float, seed: int, workdir: str,
             deposed = {d["id"] for d in s2.get("deposed", [])}
             for p in c.peers:
                 if p.id in deposed:
-                    await c.rebuild_peer(p, timeout_s=120)
+                    await rebuild(p)
                 elif not p.alive():
                     p.start()
             await c.wait_cluster(
@@ -396,6 +415,10 @@ def main(argv=None) -> int:
                     default=None,
                     help="waldb engine only: checkpoint_mode for every "
                          "peer (default: the engine's, full)")
+    ap.add_argument("--rebuild-mode", choices=("restore", "rewind"),
+                    default="restore",
+                    help="how a deposed peer is healed: a full restore, "
+                         "or a WAL rewind with the restore as fallback")
     ap.add_argument("-d", "--dir", default=None)
     ns = ap.parse_args(argv)
     workdir = ns.dir or tempfile.mkdtemp(prefix="manatee-soak-")
@@ -405,7 +428,8 @@ def main(argv=None) -> int:
                                  zk_ensemble=ns.zk_ensemble,
                                  checkpoint_mode=ns.checkpoint_mode,
                                  zk_disconnect_grace_ms=(
-                                     ns.zk_disconnect_grace_ms)))
+                                     ns.zk_disconnect_grace_ms),
+                                 rebuild_mode=ns.rebuild_mode))
     finally:
         if ns.dir is None:
             shutil.rmtree(workdir, ignore_errors=True)
