@@ -57,6 +57,7 @@ ZCONNECTIONLOSS = -4
 ZMARSHALLINGERROR = -5
 ZUNIMPLEMENTED = -6
 ZOPERATIONTIMEOUT = -7
+ZBADARGUMENTS = -8
 ZAPIERROR = -100
 ZNONODE = -101
 ZNOAUTH = -102
@@ -79,7 +80,7 @@ ERROR_NAMES = {
     ZRUNTIMEINCONSISTENCY: "RUNTIME_INCONSISTENCY",
     ZMARSHALLINGERROR: "MARSHALLING_ERROR", ZUNIMPLEMENTED: "UNIMPLEMENTED",
     ZOPERATIONTIMEOUT: "OPERATION_TIMEOUT", ZAPIERROR: "API_ERROR",
-    ZSYSTEMERROR: "SYSTEM_ERROR",
+    ZSYSTEMERROR: "SYSTEM_ERROR", ZBADARGUMENTS: "BAD_ARGUMENTS",
 }
 
 # ---------------------------------------------------------------- create modes
@@ -162,17 +163,25 @@ class Reader:
         self._buf = buf
         self._pos = 0
 
+    # every short read raises ValueError, as the native reader does: the
+    # servers answer ZMARSHALLINGERROR for it under either codec
     def int32(self) -> int:
+        if len(self._buf) - self._pos < 4:
+            raise ValueError("short buffer")
         v = struct.unpack_from(">i", self._buf, self._pos)[0]
         self._pos += 4
         return v
 
     def int64(self) -> int:
+        if len(self._buf) - self._pos < 8:
+            raise ValueError("short buffer")
         v = struct.unpack_from(">q", self._buf, self._pos)[0]
         self._pos += 8
         return v
 
     def boolean(self) -> bool:
+        if len(self._buf) - self._pos < 1:
+            raise ValueError("short buffer")
         v = self._buf[self._pos] != 0
         self._pos += 1
         return v

@@ -49,11 +49,9 @@ from typing import Any, Callable, Dict, List, Optional, Set, Tuple
 from ..common import dial
 from ..common.logging import Logger, null_logger
 from . import jute
-from .jute import (MultiOp, Reader, ZkError, ZOK, ZNONODE, ZNODEEXISTS,
-                   ZBADVERSION, ZNOTEMPTY, ZNOCHILDRENFOREPHEMERALS,
-                   ZSESSIONEXPIRED, ZMARSHALLINGERROR)
+from .jute import Reader, ZkError, ZOK, ZSESSIONEXPIRED, ZMARSHALLINGERROR
 from .quorum import LEADER, QuorumCore
-from .zkserver import ZkServer, _Node, _Session, _parent, _validate_path
+from .zkserver import ZkServer, _Node, _Session, _parent
 
 FOUR_LETTER_WORDS = (b"ruok", b"srvr")
 _WRITE_OPS = (jute.OP_CREATE, jute.OP_DELETE, jute.OP_SETDATA,
@@ -277,19 +275,6 @@ class _PeerLink:
             self._task.cancel()
         if self.writer is not None:
             self._drop(self.writer)
-
-
-class _MultiView:
-    """What the earlier ops of one multi have done to the tree, as far as
-    validating the later ones needs to know."""
-
-    __slots__ = ("made", "gone", "versions", "seqs")
-
-    def __init__(self):
-        self.made: Dict[str, bool] = {}      # created path -> ephemeral?
-        self.gone: Set[str] = set()          # deleted paths
-        self.versions: Dict[str, int] = {}   # data version after setDatas
-        self.seqs: Dict[str, int] = {}       # parent -> next sequence no.
 
 
 class ZkQuorumServer(ZkServer):
@@ -734,32 +719,11 @@ class ZkQuorumServer(ZkServer):
         res = self._apply_one(txn, zxid, txn.get("time", 0))
         return res[1] if len(res) > 1 else None
 
-    def _apply_one(self, txn: dict, zxid: int, now_ms: int) -> tuple:
-        op = txn["op"]
-        if op == "create":
-            owner = txn["owner"]
-            path = self._do_create(
-                txn["path"], bytes.fromhex(txn["data"]),
-                jute.EPHEMERAL if owner else jute.PERSISTENT, owner,
-                journal=False, zxid=zxid, now_ms=now_ms)
-            if txn.get("seq") is not None:
-                self.nodes[_parent(path)].next_seq = txn["seq"] + 1
-            return ("create", path)
-        if op == "setData":
-            return ("setData", self._do_set_data(
-                txn["path"], bytes.fromhex(txn["data"]), -1, journal=False,
-                zxid=zxid, now_ms=now_ms))
-        if op == "delete":
-            self._do_delete(txn["path"], -1, force=True, journal=False,
-                            zxid=zxid)
-            return ("delete",)
-        return ("check",)
-
     # ----------------------------------------- validation (leader, pre-log)
     # Requests are checked against the applied tree, under the proposal
-    # lock.  Inside a multi the ops see each other's effects, in order,
-    # through a _MultiView: paths created and deleted so far, data
-    # versions bumped so far, sequence numbers handed out so far.
+    # lock, by ZkServer._prep_create / _prep_versioned / _prep_multi: the
+    # one statement of the tree's rules, which the standalone server's
+    # multi goes through as well.
     def _check_owner(self, sid: int) -> None:
         """The session a write comes from must still be alive HERE, at
         the head of the proposal queue: its close or expiry may have been
@@ -767,74 +731,6 @@ class ZkQuorumServer(ZkServer):
         that would have no owner to be deleted with."""
         if sid not in self.sessions or sid in self._closing_sids:
             raise ZkError(ZSESSIONEXPIRED)
-
-    def _prep_create(self, path: str, data: bytes, flags: int, sid: int,
-                     view: Optional["_MultiView"] = None) -> dict:
-        view = view or _MultiView()
-        _validate_path(path)
-        pp = _parent(path)
-        parent = None if pp in view.gone else self.nodes.get(pp)
-        if parent is None and pp not in view.made:
-            raise ZkError(ZNONODE, pp)
-        if (parent.ephemeral_owner if parent is not None
-                else view.made[pp]):
-            raise ZkError(ZNOCHILDRENFOREPHEMERALS, pp)
-        seq = None
-        if flags in (jute.PERSISTENT_SEQUENTIAL, jute.EPHEMERAL_SEQUENTIAL):
-            seq = view.seqs.get(
-                pp, parent.next_seq if parent is not None else 0)
-            view.seqs[pp] = seq + 1
-            path = "%s%010d" % (path, seq)
-        if (path in self.nodes and path not in view.gone) \
-                or path in view.made:
-            raise ZkError(ZNODEEXISTS, path)
-        ephemeral = flags in (jute.EPHEMERAL, jute.EPHEMERAL_SEQUENTIAL)
-        if ephemeral:
-            self._check_owner(sid)
-        view.made[path] = ephemeral
-        view.gone.discard(path)
-        view.versions[path] = 0
-        return {"op": "create", "path": path, "data": data.hex(),
-                "owner": sid if ephemeral else 0, "seq": seq}
-
-    def _prep_versioned(self, op: str, path: str, version: int,
-                        data: bytes = b"",
-                        view: Optional["_MultiView"] = None) -> dict:
-        view = view or _MultiView()
-        node = None if path in view.gone else self.nodes.get(path)
-        if node is None and path not in view.made:
-            raise ZkError(ZNONODE, path)
-        if op == "delete":
-            kids = {"%s/%s" % (path.rstrip("/"), c)
-                    for c in (node.children if node is not None else ())}
-            kids |= {p for p in view.made if _parent(p) == path}
-            if kids - view.gone:
-                raise ZkError(ZNOTEMPTY, path)
-        current = view.versions.get(
-            path, node.version if node is not None else 0)
-        if version != -1 and version != current:
-            raise ZkError(ZBADVERSION, path)
-        if op == "setData":
-            view.versions[path] = current + 1
-            return {"op": op, "path": path, "data": data.hex()}
-        if op == "delete":
-            view.made.pop(path, None)
-            view.versions.pop(path, None)
-            view.gone.add(path)
-        return {"op": op, "path": path}
-
-    def _prep_multi(self, ops: List[MultiOp], sid: int) -> List[dict]:
-        view = _MultiView()
-        out = []
-        for op in ops:
-            if op.kind == "create":
-                out.append(self._prep_create(op.path, op.data or b"",
-                                             op.flags, sid, view))
-            else:
-                out.append(self._prep_versioned(op.kind, op.path,
-                                                op.version, op.data or b"",
-                                                view))
-        return out
 
     # ------------------------------------------------------ client handling
     def _four_letter(self, word: bytes) -> bytes:

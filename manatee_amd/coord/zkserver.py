@@ -36,7 +36,8 @@ from ..common.logging import Logger, null_logger
 from . import jute
 from .jute import (MultiOp, Reader, Stat, Writer, ZkError, ZOK, ZNONODE,
                    ZNODEEXISTS, ZBADVERSION, ZNOTEMPTY, ZSESSIONEXPIRED,
-                   ZNOCHILDRENFOREPHEMERALS, ZUNIMPLEMENTED, ZMARSHALLINGERROR)
+                   ZNOCHILDRENFOREPHEMERALS, ZUNIMPLEMENTED, ZMARSHALLINGERROR,
+                   ZBADARGUMENTS)
 
 
 def _now_ms() -> int:
@@ -101,6 +102,48 @@ def _validate_path(path: str) -> str:
     if not path.startswith("/") or (len(path) > 1 and path.endswith("/")):
         raise ZkError(jute.ZAPIERROR, path)
     return path
+
+
+def _child_name(parent_path: str, path: str) -> str:
+    return path[len(parent_path):].lstrip("/")
+
+
+class _Shadow:
+    """One znode as the later ops of a transaction see it: only what
+    validation reads."""
+
+    __slots__ = ("ephemeral", "version", "next_seq", "children")
+
+    def __init__(self, ephemeral: bool, version: int = 0, next_seq: int = 0,
+                 children: Optional[Set[str]] = None):
+        self.ephemeral = ephemeral
+        self.version = version
+        self.next_seq = next_seq
+        self.children: Set[str] = children if children is not None else set()
+
+
+class _MultiView:
+    """The tree as one transaction sees it while it is validated: the
+    applied tree, overlaid with what the transaction's earlier ops have
+    done.  A path is copied into the overlay when it is first looked at;
+    ``None`` there means deleted (or never there)."""
+
+    __slots__ = ("_nodes", "_seen")
+
+    def __init__(self, nodes: Dict[str, _Node]):
+        self._nodes = nodes
+        self._seen: Dict[str, Optional[_Shadow]] = {}
+
+    def get(self, path: str) -> Optional[_Shadow]:
+        if path not in self._seen:
+            n = self._nodes.get(path)
+            self._seen[path] = None if n is None else _Shadow(
+                bool(n.ephemeral_owner), n.version, n.next_seq,
+                set(n.children))
+        return self._seen[path]
+
+    def put(self, path: str, shadow: Optional[_Shadow]) -> None:
+        self._seen[path] = shadow
 
 
 class ZkServer:
@@ -349,18 +392,22 @@ class ZkServer:
             raise ZkError(ZNONODE, parent_path)
         if parent.ephemeral_owner:
             raise ZkError(ZNOCHILDRENFOREPHEMERALS, parent_path)
-        if flags in (jute.PERSISTENT_SEQUENTIAL, jute.EPHEMERAL_SEQUENTIAL):
+        sequential = flags in (jute.PERSISTENT_SEQUENTIAL,
+                               jute.EPHEMERAL_SEQUENTIAL)
+        if sequential:
             path = "%s%010d" % (path, parent.next_seq)
-            parent.next_seq += 1
         if path in self.nodes:
             raise ZkError(ZNODEEXISTS, path)
+        if sequential:
+            # only a create that succeeds consumes a sequence number
+            parent.next_seq += 1
         self.zxid = self.zxid + 1 if zxid is None else zxid
         ephemeral = flags in (jute.EPHEMERAL, jute.EPHEMERAL_SEQUENTIAL)
         node = _Node(data, self.zxid,
                      ephemeral_owner=owner_sid if ephemeral else 0,
                      now_ms=now_ms)
         self.nodes[path] = node
-        parent.children.add(path[len(parent_path):].lstrip("/"))
+        parent.children.add(_child_name(parent_path, path))
         parent.cversion += 1
         parent.pzxid = self.zxid
         if ephemeral and owner_sid in self.sessions:
@@ -374,6 +421,10 @@ class ZkServer:
 
     def _do_delete(self, path: str, version: int, force: bool = False,
                    journal: bool = True, zxid: Optional[int] = None) -> None:
+        if path == "/":
+            # the root is not a znode anybody made; without it every
+            # later create would answer ZNONODE
+            raise ZkError(ZBADARGUMENTS, path)
         node = self.nodes.get(path)
         if node is None:
             raise ZkError(ZNONODE, path)
@@ -386,7 +437,7 @@ class ZkServer:
         parent_path = _parent(path)
         parent = self.nodes.get(parent_path)
         if parent is not None:
-            parent.children.discard(path[len(parent_path):].lstrip("/"))
+            parent.children.discard(_child_name(parent_path, path))
             parent.cversion += 1
             parent.pzxid = self.zxid
         if node.ephemeral_owner and node.ephemeral_owner in self.sessions:
@@ -417,40 +468,111 @@ class ZkServer:
         return node.stat()
 
     def _do_multi(self, ops: List[MultiOp], owner_sid: int) -> List[tuple]:
-        # validate-then-apply so the transaction is atomic
+        # validate the whole transaction first, every op seeing the
+        # effects of the earlier ones; a failure raises from here with
+        # nothing applied, journaled, fired or numbered
         # (ref zookeeperMgr.js:605-630 relies on this for putClusterState CAS)
+        txns = self._prep_multi(ops, owner_sid)
+        return [self._apply_one(txn, None, None, journal=True)
+                for txn in txns]
+
+    # ------------------------------------------------ validation and apply
+    # A write is validated into its OUTCOME (a create with its final,
+    # already-sequenced path), then applied.  The standalone server does
+    # this for a multi; the quorum server (zkquorum.py) for every write,
+    # with the log between the two halves.  Inside a multi the ops see
+    # each other's effects, in order, through a _MultiView.
+    def _check_owner(self, sid: int) -> None:
+        """An ephemeral needs a live session to be deleted with."""
+        if sid not in self.sessions:
+            raise ZkError(ZSESSIONEXPIRED)
+
+    def _prep_create(self, path: str, data: bytes, flags: int, sid: int,
+                     view: Optional[_MultiView] = None) -> dict:
+        view = view or _MultiView(self.nodes)
+        _validate_path(path)
+        pp = _parent(path)
+        parent = view.get(pp)
+        if parent is None:
+            raise ZkError(ZNONODE, pp)
+        if parent.ephemeral:
+            raise ZkError(ZNOCHILDRENFOREPHEMERALS, pp)
+        seq = None
+        if flags in (jute.PERSISTENT_SEQUENTIAL, jute.EPHEMERAL_SEQUENTIAL):
+            seq = parent.next_seq
+            path = "%s%010d" % (path, seq)
+        if view.get(path) is not None:
+            raise ZkError(ZNODEEXISTS, path)
+        ephemeral = flags in (jute.EPHEMERAL, jute.EPHEMERAL_SEQUENTIAL)
+        if ephemeral:
+            self._check_owner(sid)
+        if seq is not None:
+            parent.next_seq = seq + 1
+        parent.children.add(_child_name(pp, path))
+        view.put(path, _Shadow(ephemeral))
+        return {"op": "create", "path": path, "data": data.hex(),
+                "owner": sid if ephemeral else 0, "seq": seq}
+
+    def _prep_versioned(self, op: str, path: str, version: int,
+                        data: bytes = b"",
+                        view: Optional[_MultiView] = None) -> dict:
+        view = view or _MultiView(self.nodes)
+        if op == "delete" and path == "/":
+            raise ZkError(ZBADARGUMENTS, path)
+        node = view.get(path)
+        if node is None:
+            raise ZkError(ZNONODE, path)
+        if op == "delete" and node.children:
+            raise ZkError(ZNOTEMPTY, path)
+        if version != -1 and version != node.version:
+            raise ZkError(ZBADVERSION, path)
+        if op == "setData":
+            node.version += 1
+            return {"op": op, "path": path, "data": data.hex()}
+        if op == "delete":
+            view.put(path, None)
+            pp = _parent(path)
+            parent = view.get(pp)
+            if parent is not None:
+                parent.children.discard(_child_name(pp, path))
+        return {"op": op, "path": path}
+
+    def _prep_multi(self, ops: List[MultiOp], sid: int) -> List[dict]:
+        view = _MultiView(self.nodes)
+        out = []
         for op in ops:
             if op.kind == "create":
-                pp = _parent(op.path)
-                parent = self.nodes.get(pp)
-                if parent is None:
-                    raise ZkError(ZNONODE, pp)
-                if op.flags == jute.PERSISTENT and op.path in self.nodes:
-                    raise ZkError(ZNODEEXISTS, op.path)
-            elif op.kind in ("setData", "check", "delete"):
-                node = self.nodes.get(op.path)
-                if node is None:
-                    raise ZkError(ZNONODE, op.path)
-                if op.version != -1 and node.version != op.version:
-                    raise ZkError(ZBADVERSION, op.path)
-                if op.kind == "delete" and node.children:
-                    raise ZkError(ZNOTEMPTY, op.path)
-        results: List[tuple] = []
-        for op in ops:
-            if op.kind == "create":
-                results.append(("create",
-                                self._do_create(op.path, op.data or b"",
-                                                op.flags, owner_sid)))
-            elif op.kind == "setData":
-                results.append(("setData",
-                                self._do_set_data(op.path, op.data or b"",
-                                                  op.version)))
-            elif op.kind == "delete":
-                self._do_delete(op.path, op.version)
-                results.append(("delete",))
+                out.append(self._prep_create(op.path, op.data or b"",
+                                             op.flags, sid, view))
             else:
-                results.append(("check",))
-        return results
+                out.append(self._prep_versioned(op.kind, op.path,
+                                                op.version, op.data or b"",
+                                                view))
+        return out
+
+    def _apply_one(self, txn: dict, zxid: Optional[int],
+                   now_ms: Optional[int], journal: bool = False) -> tuple:
+        """Apply one validated outcome; cannot fail for a txn that
+        ``_prep_*`` produced against this tree."""
+        op = txn["op"]
+        if op == "create":
+            owner = txn["owner"]
+            path = self._do_create(
+                txn["path"], bytes.fromhex(txn["data"]),
+                jute.EPHEMERAL if owner else jute.PERSISTENT, owner,
+                journal=journal, zxid=zxid, now_ms=now_ms)
+            if txn.get("seq") is not None:
+                self.nodes[_parent(path)].next_seq = txn["seq"] + 1
+            return ("create", path)
+        if op == "setData":
+            return ("setData", self._do_set_data(
+                txn["path"], bytes.fromhex(txn["data"]), -1, journal=journal,
+                zxid=zxid, now_ms=now_ms))
+        if op == "delete":
+            self._do_delete(txn["path"], -1, force=True, journal=journal,
+                            zxid=zxid)
+            return ("delete",)
+        return ("check",)
 
     # -------------------------------------------------------- conn handling
     async def _read_frame(self, reader: asyncio.StreamReader) -> Optional[bytes]:

@@ -80,6 +80,24 @@ def test_reader_short_buffer_raises():
     nr = jute.Reader(b"\x00\x00\x00\x05ab")   # buffer claims 5, has 2
     with pytest.raises(ValueError):
         nr.buffer()
+    # both readers, every primitive: a short read is a ValueError (the
+    # servers answer ZMARSHALLINGERROR for exactly that)
+    short = {"int32": [b"", b"\x00\x00\x00"],
+             "int64": [b"", b"\x00" * 7],
+             "boolean": [b""],
+             "buffer": [b"", b"\x00\x00", b"\x00\x00\x00\x05ab",
+                        b"\x00\x00\x00\x01"],
+             "ustring": [b"", b"\x00\x00\x00", b"\x00\x00\x00\x03ab"]}
+    for reader in (jute.Reader, jute.PyReader):
+        for op, inputs in short.items():
+            for buf in inputs:
+                with pytest.raises(ValueError):
+                    getattr(reader(buf), op)()
+                # ... and after a good read that leaves too little behind
+                with pytest.raises(ValueError):
+                    r = reader(b"\x00\x00\x00\x07" + buf)
+                    assert r.int32() == 7
+                    getattr(r, op)()
 
 
 def test_int32_range_enforced():

@@ -166,6 +166,209 @@ def test_multi_transaction_cas():
     run(go())
 
 
+def test_failed_multi_fires_no_watch():
+    """A multi whose second op fails leaves the first one undone: no
+    watcher hears of it and the node reads back unchanged.  Then a multi
+    that makes a parent and its child in one go is accepted."""
+    async def go():
+        srv, cli = await _pair()
+        watcher = ZkClient(srv.conn_str, session_timeout_ms=4000)
+        await watcher.connect()
+        events = []
+        try:
+            await cli.create("/x", b"0")
+            root_children = asyncio.get_running_loop().create_future()
+
+            def on_event(etype, path):
+                events.append((etype, path))
+                if (etype, path) == (jute.EVENT_NODE_CHILDREN_CHANGED, "/") \
+                        and not root_children.done():
+                    root_children.set_result(None)
+
+            for path in ("/x", "/"):
+                await watcher.get_data(path, watch=on_event)
+                await watcher.get_children(path, watch=on_event)
+            with pytest.raises(jute.ZkError) as ei:
+                await cli.multi([
+                    jute.MultiOp.set_data("/x", b"1", version=0),
+                    jute.MultiOp.set_data("/x", b"2", version=0)])
+            assert ei.value.code == jute.ZBADVERSION
+            # the server writes an event to the watcher's connection
+            # while it applies the write, so one would be ahead of this
+            # reply on the same stream
+            data, stat = await watcher.get_data("/x")
+            assert events == []
+            assert srv.stats["watch_events"] == 0
+            assert (data, stat.version, stat.mzxid) == (b"0", 0, stat.czxid)
+
+            res = await cli.multi([jute.MultiOp.create("/p", b"P"),
+                                   jute.MultiOp.create("/p/c", b"C")])
+            assert res == [("create", "/p"), ("create", "/p/c")]
+            assert (await cli.get_data("/p"))[0] == b"P"
+            assert (await cli.get_data("/p/c"))[0] == b"C"
+            assert (await cli.get_children("/p"))[0] == ["c"]
+            await asyncio.wait_for(root_children, 5)
+            assert events == [(jute.EVENT_NODE_CHILDREN_CHANGED, "/")]
+        finally:
+            await watcher.close()
+            await cli.close()
+            await srv.stop()
+    run(go())
+
+
+# ------------------------------------------------ truncated request bodies
+def _request_bodies():
+    """opcode -> a valid request body (what follows the request header),
+    one for every opcode ``_dispatch`` handles."""
+    def body(build):
+        w = jute.PyWriter()
+        build(w)
+        return w.tobytes()
+
+    def create(w):
+        w.ustring("/new").buffer(b"data")
+        jute.write_acls(w)
+        w.int32(jute.PERSISTENT)
+
+    def set_watches(w):
+        w.int64(0)
+        w.int32(1).ustring("/x")
+        w.int32(2).ustring("/nope").ustring("/x")
+        w.int32(1).ustring("/")
+
+    path_watch = body(lambda w: w.ustring("/x").boolean(True))
+    return {
+        jute.OP_PING: b"",
+        jute.OP_CREATE: body(create),
+        jute.OP_DELETE: body(lambda w: w.ustring("/gone").int32(-1)),
+        jute.OP_EXISTS: path_watch,
+        jute.OP_GETDATA: path_watch,
+        jute.OP_SETDATA: body(
+            lambda w: w.ustring("/x").buffer(b"v1").int32(0)),
+        jute.OP_GETCHILDREN: path_watch,
+        jute.OP_GETCHILDREN2: path_watch,
+        jute.OP_MULTI: body(lambda w: jute.write_multi_request(w, [
+            jute.MultiOp.create("/m", b"m"),
+            jute.MultiOp.set_data("/x", b"v2", 0),
+            jute.MultiOp.delete("/gone", -1),
+            jute.MultiOp.check("/", -1)])),
+        jute.OP_SYNC: body(lambda w: w.ustring("/x")),
+        jute.OP_AUTH: body(lambda w: w.int32(0).ustring("digest")
+                           .buffer(b"user:pw")),
+        jute.OP_SETWATCHES: body(set_watches),
+        jute.OP_GETACL: body(lambda w: w.ustring("/x")),     # unimplemented
+    }
+
+
+def _truncation_server():
+    from manatee_amd.coord.zkserver import _Session
+    srv = ZkServer()
+    sess = _Session(0x51, b"\x00" * 16, 30000)
+    srv.sessions[sess.sid] = sess
+    for path in ("/x", "/gone"):
+        srv._do_create(path, b"v0", jute.PERSISTENT, sess.sid, now_ms=1)
+    return srv, sess
+
+
+def _tree_of(srv):
+    return {p: (n.data, n.version, n.cversion, sorted(n.children),
+                n.ephemeral_owner, n.next_seq, n.stat_czxid, n.stat_mzxid,
+                n.pzxid) for p, n in srv.nodes.items()}
+
+
+def _reply_error(frame, xid):
+    """Check that ``frame`` is one well-formed reply; return its error."""
+    r = jute.PyReader(frame)
+    assert r.int32() == len(frame) - 4, "length prefix"
+    got_xid, _zxid, err = jute.decode_reply_header(r)
+    assert got_xid in (xid, jute.XID_PING, jute.XID_AUTH,
+                       jute.XID_SET_WATCHES)
+    return err
+
+
+_READERS = [jute.PyReader] + ([jute.Reader] if jute.CODEC == "native" else [])
+# opcodes whose handler reads nothing of the body
+_BODYLESS = (jute.OP_PING, jute.OP_AUTH)
+
+
+@pytest.mark.parametrize("opcode", sorted(_request_bodies()))
+def test_truncated_request_body_gets_marshalling_error(opcode):
+    """Every proper prefix of a request body is answered with one
+    well-formed ZMARSHALLINGERROR reply, under either jute codec alike,
+    and leaves the tree alone; the whole body gets the normal reply."""
+    body = _request_bodies()[opcode]
+    xid = 7
+    for cut in range(len(body) + 1):
+        replies = []
+        for reader in _READERS:
+            srv, sess = _truncation_server()
+            before = _tree_of(srv)
+            frame = srv._dispatch(sess, xid, opcode, reader(body[:cut]))
+            err = _reply_error(frame, xid)
+            if opcode == jute.OP_GETACL:
+                assert err == jute.ZUNIMPLEMENTED
+            elif cut < len(body) and opcode not in _BODYLESS:
+                assert err == jute.ZMARSHALLINGERROR, (cut, reader, err)
+                assert _tree_of(srv) == before, (cut, reader)
+            else:
+                assert err == jute.ZOK, (cut, reader, err)
+            if cut == len(body) and opcode in (jute.OP_SETDATA,
+                                               jute.OP_MULTI):
+                # these replies carry an mtime from the server's clock
+                st = jute.Stat.read(jute.PyReader(frame[20:])) \
+                    if opcode == jute.OP_SETDATA else \
+                    jute.read_multi_response(jute.PyReader(frame[20:]))[1][1]
+                assert (st.version, st.dataLength) == (1, 2)
+                replies.append((len(frame), frame[:20], _tree_of(srv)))
+            else:
+                replies.append((frame, _tree_of(srv)))
+        assert all(r == replies[0] for r in replies), \
+            "the codecs disagree at cut %d" % cut
+    # the whole bodies did what they say
+    srv, sess = _truncation_server()
+    for op in (jute.OP_CREATE, jute.OP_DELETE, jute.OP_SETDATA):
+        srv._dispatch(sess, xid, op, jute.PyReader(_request_bodies()[op]))
+    assert sorted(srv.nodes) == ["/", "/new", "/x"]
+    assert srv.nodes["/x"].data == b"v1"
+
+
+@pytest.mark.parametrize("opcode", [jute.OP_CREATE, jute.OP_DELETE,
+                                    jute.OP_SETDATA, jute.OP_MULTI,
+                                    jute.OP_SETWATCHES])
+def test_truncated_request_body_quorum_server(opcode, tmp_path):
+    """The replicated server parses writes and SetWatches in code of its
+    own: the same answer there, before anything is proposed."""
+    from manatee_amd.coord.zkquorum import ZkQuorumServer
+    from manatee_amd.coord.zkserver import _Session
+    srv = ZkQuorumServer(1, peers={1: ("127.0.0.1", 1)},
+                         data_dir=str(tmp_path / "m1"))
+    sess = _Session(0x51, b"\x00" * 16, 30000)
+    srv.sessions[sess.sid] = sess
+    srv._do_create("/x", b"v0", jute.PERSISTENT, sess.sid, now_ms=1)
+    before = _tree_of(srv)
+    body = _request_bodies()[opcode]
+    xid = 7
+    for cut in range(len(body)):
+        replies = []
+        for reader in _READERS:
+            r = reader(body[:cut])
+            if opcode == jute.OP_SETWATCHES:
+                frame = srv._dispatch(sess, xid, opcode, r)
+            else:
+                # a body that does not parse is answered before the
+                # first await
+                coro = srv._dispatch_write(sess, xid, opcode, r)
+                with pytest.raises(StopIteration) as done:
+                    coro.send(None)
+                frame = done.value.value
+            assert _reply_error(frame, xid) == jute.ZMARSHALLINGERROR, \
+                (cut, reader)
+            replies.append(frame)
+        assert all(f == replies[0] for f in replies)
+    assert _tree_of(srv) == before
+    assert not srv.data_watches and not srv.child_watches
+
+
 def test_session_expiry_removes_ephemerals():
     async def go():
         srv = ZkServer(tick_ms=50, min_session_timeout_ms=200)

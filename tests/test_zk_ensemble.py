@@ -775,6 +775,63 @@ def test_multi_ops_see_each_other_in_order(tmp_path):
     run(go())
 
 
+def test_failed_multi_fires_no_watch(tmp_path):
+    """A multi whose second op fails is never logged: no watcher hears
+    of its first op and the node reads back unchanged, on every member.
+    Then a multi that makes a parent and its child is accepted."""
+    async def go():
+        ens = await Ensemble(tmp_path).start()
+        cli = watcher = None
+        events = []
+        try:
+            lead = ens.members[await ens.wait_leader()]
+            cli = await _client(ens.conn_str)
+            watcher = await _client(ens.conn_str)
+            await cli.create("/x", b"0")
+            root_children = asyncio.get_running_loop().create_future()
+
+            def on_event(etype, path):
+                events.append((etype, path))
+                if (etype, path) == (jute.EVENT_NODE_CHILDREN_CHANGED, "/") \
+                        and not root_children.done():
+                    root_children.set_result(None)
+
+            for path in ("/x", "/"):
+                await watcher.get_data(path, watch=on_event)
+                await watcher.get_children(path, watch=on_event)
+            fired = lead.stats["watch_events"]
+            proposals = lead.stats["proposals"]
+            with pytest.raises(ZkError) as ei:
+                await cli.multi([MultiOp.set_data("/x", b"1", version=0),
+                                 MultiOp.set_data("/x", b"2", version=0)])
+            assert ei.value.code == jute.ZBADVERSION
+            # an event is written to the watcher's connection when the
+            # write is applied, so one would be ahead of this reply
+            data, stat = await watcher.get_data("/x")
+            assert events == []
+            assert lead.stats["watch_events"] == fired
+            assert lead.stats["proposals"] == proposals
+            assert (data, stat.version, stat.mzxid) == (b"0", 0, stat.czxid)
+
+            res = await cli.multi([MultiOp.create("/p", b"P"),
+                                   MultiOp.create("/p/c", b"C")])
+            assert res == [("create", "/p"), ("create", "/p/c")]
+            assert (await cli.get_data("/p"))[0] == b"P"
+            assert (await cli.get_data("/p/c"))[0] == b"C"
+            assert (await cli.get_children("/p"))[0] == ["c"]
+            await asyncio.wait_for(root_children, 5)
+            assert events == [(jute.EVENT_NODE_CHILDREN_CHANGED, "/")]
+            await ens.settled()
+            full = ens.assert_identical()
+            assert full["nodes"]["/x"]["version"] == 0
+        finally:
+            for c in (cli, watcher):
+                if c is not None:
+                    await c.close()
+            await ens.stop()
+    run(go())
+
+
 def test_no_ephemeral_for_a_session_whose_close_is_already_logged(tmp_path):
     """A create that reaches the head of the proposal queue after its own
     session's close must not leave an ownerless ephemeral behind."""
