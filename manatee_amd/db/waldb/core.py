@@ -25,7 +25,6 @@ import struct
 import sys
 import time
 import uuid
-import zlib
 from typing import Dict, Iterator, List, Optional, Tuple
 
 from ...common import dial
@@ -706,8 +705,19 @@ class ReplCore:
             writer.write(b'{"ok":false,"error":"ident-mismatch"}\n')
             await writer.drain()
             return
-        err = self._check_follower(int(req.get("timeline", 0)),
-                                   int(req.get("start_lsn", 0)))
+        # a follower that sends neither is judged, and answered, by the
+        # rule from before the handshake carried them
+        f_history = req.get("history")
+        if not isinstance(f_history, list):
+            f_history = None
+        start = int(req.get("start_lsn", 0))
+        err = self._check_follower(int(req.get("timeline", 0)), start,
+                                   f_history)
+        offer = None
+        if not err and "wal_start" in req:
+            offer, err = await self._handshake_offer(
+                int(req["wal_start"]), int(req.get("timeline", 0)), start,
+                f_history)
         if err:
             writer.write(json.dumps({"ok": False, "error": err})
                          .encode() + b"\n")
@@ -717,6 +727,7 @@ class ReplCore:
             return
         resp = {"ok": True, "timeline": self.timeline,
                 "history": self.history}
+        resp.update(offer or {})
         writer.write((json.dumps(resp) + "\n").encode())
         await writer.drain()
         # A reconnect under the same name supersedes any stale sender:
@@ -820,24 +831,42 @@ class ReplCore:
         name = self.settings.sync_standby
         return next((r for r in self.replicas if r.name == name), None)
 
-    def _check_follower(self, timeline: int, start_lsn: int) -> Optional[str]:
-        """May a follower at (timeline, start_lsn) stream from us?
-        Returns an error string or None."""
-        if timeline > self.timeline:
-            return "timeline-mismatch"
-        if timeline < self.timeline:
-            # follower must not have WAL past our switch to any later
-            # timeline — that WAL belongs to a deposed line of history
-            for h in self.history:
-                if h["tl"] > timeline and start_lsn > h["at"]:
-                    return "diverged"
-        if start_lsn > self.wal.end:
-            return "diverged"
-        if start_lsn < self.wal.start:
-            # the WAL this follower needs was recycled by a checkpoint;
-            # it must bootstrap from a snapshot instead
-            return "wal-gone"
-        return None
+    def _check_follower(self, timeline: int, start_lsn: int,
+                        history: Optional[List[dict]] = None
+                        ) -> Optional[str]:
+        """May a follower at (timeline, start_lsn) with ``history`` (None:
+        it sent none) stream from us?  Returns an error string or None;
+        the rules are ``rewind.check_follower``."""
+        return rewindmod.check_follower(
+            timeline, history, start_lsn, self.timeline, self.history,
+            self.wal.start, self.wal.end)
+
+    def _wal_range(self, lo: int, hi: int) -> bytes:
+        return self.wal.read(lo, hi - lo)
+
+    async def _handshake_offer(self, f_start: int, timeline: int,
+                               start_lsn: int,
+                               history: Optional[List[dict]]):
+        """``(offer, None)`` for a follower ``_check_follower`` accepted —
+        the CRC-32 of our WAL in the window below ``start_lsn``, which it
+        compares with its own bytes (``rewind.handshake_offer``) — or
+        ``(None, error)`` if a checkpoint recycled what it needs while
+        the window was read."""
+        while True:
+            window = rewindmod.probe_window(f_start, self.wal.start,
+                                            start_lsn)
+            crc = 0
+            try:
+                # a slice at a time, like rewind_probe
+                for crc in rewindmod.crc_slices(self._wal_range, window,
+                                                start_lsn):
+                    await asyncio.sleep(0)
+            except (WalGone, IOError):
+                err = self._check_follower(timeline, start_lsn, history)
+                if err or window >= self.wal.start:
+                    return None, err or "wal-gone"
+                continue
+            return {"window_start": window, "crc32": crc}, None
 
     async def rewind_probe(self, req: dict) -> dict:
         """Answer a diverged peer that wants to rewind (``rewind.py``):
@@ -859,17 +888,11 @@ class ReplCore:
             return {"ok": False, "error": "unverifiable"}
         # a slice at a time: one CRC over the whole window would hold
         # the event loop (and every commit ack) for its duration
-        crc, pos = 0, start
+        crc = 0
         try:
-            while pos < fork:
-                data = self.wal.read(
-                    pos, min(rewindmod.CRC_CHUNK, fork - pos))
-                if not data:
-                    return {"ok": False, "error": "unverifiable"}
-                crc = zlib.crc32(data, crc)
-                pos += len(data)
+            for crc in rewindmod.crc_slices(self._wal_range, start, fork):
                 await asyncio.sleep(0)
-        except WalGone:
+        except (WalGone, IOError):
             # a checkpoint recycled the window while we were reading it
             return {"ok": False, "error": "unverifiable"}
         return {"ok": True, "timeline": self.timeline,
@@ -905,6 +928,20 @@ class ReplCore:
                             "replay_lsn": self.replay_lsn})
                 + "\n").encode()
 
+    async def _verify_handshake(self, resp: dict) -> bool:
+        """``rewind.handshake_verify`` a slice at a time: a standby
+        serves reads while it hashes.  An answer without a window (an
+        upstream that sends none, or a follower with no WAL below its
+        end) verifies nothing and passes."""
+        end = self.wal.end
+        offered = rewindmod.offered_window(resp, end)
+        if offered is None:
+            return True
+        crc = 0
+        for crc in rewindmod.crc_slices(self._wal_range, offered[0], end):
+            await asyncio.sleep(0)
+        return crc == offered[1]
+
     async def _follow_upstream_once(self, gen: int) -> None:
         if not self.upstream:
             return
@@ -921,7 +958,9 @@ class ReplCore:
                    "name": self.settings.name,
                    "ident": self.ident.get("ident"),
                    "timeline": self.timeline,
-                   "start_lsn": self.wal.end}
+                   "start_lsn": self.wal.end,
+                   "history": self.history,
+                   "wal_start": self.wal.start}
             writer.write((json.dumps(req) + "\n").encode())
             await writer.drain()
             line = await asyncio.wait_for(reader.readline(), 5.0)
@@ -934,6 +973,16 @@ class ReplCore:
                     self.log.error("cannot stream from upstream; "
                                    "restore required", error=err)
                 raise RuntimeError("upstream refused replication: " + err)
+            # the histories did not rule us out; the bytes decide.  Before
+            # anything is adopted, appended or acked: a follower found
+            # diverged here has changed no file and opened no write gate
+            if not await self._verify_handshake(resp):
+                self.upstream_status = "diverged"
+                self.log.error("cannot stream from upstream; restore "
+                               "required", error="diverged",
+                               detail="WAL below our end differs from "
+                                      "the upstream's")
+                raise RuntimeError("WAL is not a prefix of the upstream's")
             # adopt upstream's timeline/history (we are a consistent prefix)
             if resp.get("timeline", self.timeline) != self.timeline or \
                     resp.get("history") != self.history:

@@ -34,7 +34,7 @@ import os
 import socket
 import sys
 import zlib
-from typing import Callable, List, Optional, Tuple
+from typing import Callable, Iterator, List, Optional, Tuple
 
 from ...common import dial
 from ...common import lsn as lsnmod
@@ -98,6 +98,103 @@ def probe_window(f_start: int, u_start: int, fork_lsn: int) -> int:
     """Start of the byte range both sides hash: as far below the fork
     point as both still have WAL, one read window at the most."""
     return max(int(f_start), int(u_start), fork_lsn - PROBE_WINDOW)
+
+
+def crc_slices(read: Callable[[int, int], bytes], lo: int, hi: int
+               ) -> Iterator[int]:
+    """CRC-32 of the bytes ``[lo, hi)`` that ``read(lo, hi)`` returns,
+    ``CRC_CHUNK`` at a time: yields the running value after every slice
+    (a caller on an event loop yields to it in between), the last one is
+    the CRC of the whole range.  Nothing is yielded for an empty range;
+    a read that comes back short raises ``IOError``."""
+    crc, pos = 0, lo
+    while pos < hi:
+        data = read(pos, min(pos + CRC_CHUNK, hi))
+        if not data:
+            raise IOError("no WAL bytes at %d" % pos)
+        crc = zlib.crc32(data, crc)
+        pos += len(data)
+        yield crc
+
+
+def range_crc(read: Callable[[int, int], bytes], lo: int, hi: int) -> int:
+    crc = 0
+    for crc in crc_slices(read, lo, hi):
+        pass
+    return crc
+
+
+# ------------------------------------------------- replication handshake
+# A follower may stream from ``start_lsn`` (its WAL end) only if its WAL
+# is a byte prefix of the upstream's.  The histories can rule that out
+# (``check_follower``); they cannot confirm it: two peers promoted at
+# the same offset have identical histories and different bytes after
+# it, and so has a primary that lost an unsynced tail its follower
+# holds.  So an accepted follower gets the CRC of the upstream's bytes
+# just below ``start_lsn`` (``handshake_offer``) and compares it with
+# its own before it appends or acks anything (``handshake_verify``).
+def check_follower(f_timeline: int, f_history: Optional[List[dict]],
+                   start_lsn: int, u_timeline: int, u_history: List[dict],
+                   u_start: int, u_end: int) -> Optional[str]:
+    """May a follower at ``(f_timeline, start_lsn)`` with history
+    ``f_history`` stream from an upstream with WAL ``[u_start, u_end)``?
+    Returns the refusal (``timeline-mismatch``, ``diverged``,
+    ``wal-gone``) or None.  ``f_history`` is None for a follower that
+    does not send one: then only the upstream's own switch points to
+    timelines above the follower's are held against it."""
+    if f_timeline > u_timeline:
+        return "timeline-mismatch"
+    # the follower must not have WAL past our switch to any later
+    # timeline: that WAL belongs to a deposed line of history
+    for h in u_history or []:
+        if h["tl"] > f_timeline and start_lsn > h["at"]:
+            return "diverged"
+    if start_lsn > u_end:
+        return "diverged"
+    if f_history is not None:
+        # ... nor past the point where the two histories part ways: two
+        # peers promoted apart share nothing above the lower switch
+        _tl, fork = fork_point(f_timeline, f_history, start_lsn,
+                               u_timeline, u_history, u_end)
+        if fork < start_lsn:
+            return "diverged"
+    if start_lsn < u_start:
+        # the WAL this follower needs was recycled by a checkpoint; it
+        # must bootstrap from a snapshot instead
+        return "wal-gone"
+    return None
+
+
+def handshake_offer(f_start: int, u_start: int, start_lsn: int,
+                    read: Callable[[int, int], bytes]) -> dict:
+    """What the upstream's OK answer carries for an accepted follower:
+    ``{window_start, crc32}`` of ITS bytes in ``[W, start_lsn)``,
+    ``W = probe_window(...)``.  ``W >= start_lsn`` is an empty window (a
+    freshly restored follower has no WAL below its end): CRC 0."""
+    window = probe_window(f_start, u_start, start_lsn)
+    return {"window_start": window,
+            "crc32": range_crc(read, window, start_lsn)}
+
+
+def offered_window(resp: dict, start_lsn: int) -> Optional[Tuple[int, int]]:
+    """``(W, crc)`` the follower has to check, or None when the answer
+    carries none (an upstream that does not send one) or an empty one."""
+    if "window_start" not in resp or "crc32" not in resp:
+        return None
+    window, crc = int(resp["window_start"]), int(resp["crc32"])
+    if window >= start_lsn:
+        return None
+    return window, crc
+
+
+def handshake_verify(resp: dict, start_lsn: int,
+                     read: Callable[[int, int], bytes]) -> bool:
+    """The follower's half: are its own bytes in the offered window the
+    upstream's?  True as well when there is nothing to compare."""
+    offered = offered_window(resp, start_lsn)
+    if offered is None:
+        return True
+    return range_crc(read, offered[0], start_lsn) == offered[1]
 
 
 # ---------------------------------------------------------------- result
